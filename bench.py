@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — measures the hot path per the driver contract.
 
-BASELINE.json's metric is "input rows/sec/GPU on Nexmark q7+q8"; the default
-run emits BOTH lines:
-- q7 (configs[1]): append-only HashAgg group_key=[window $expr1],
+BASELINE.json's metric is "input rows/sec/GPU on Nexmark q7+q8". A plain
+run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline
+q7 figure needs: set up, warm up, time N steps, write the outputs if
+--dump-outputs is given, print ONE result line. `--full` adds everything
+else: the oracle parity gate, the q7 full-plan and q8 lines, the
+checkpoint-inclusive q7 segment and the CPU baselines. There --steps and
+--warmup size the q7 line; the q7 full-plan and q8 lines, whose join state
+grows by 1M rows per step, run at most 500 steps after 25 warmup steps and
+report the count they ran.
+- q7 (configs[1], the headline): append-only HashAgg group_key=[window $expr1],
   aggs=[max(price), count] (reference plan `nexmark.yaml` q7 block) on
   synthetic bid-shaped chunks: price ~ uniform[1,1e7) i64, date_time
   monotone in 10s windows, all-Insert ops, seeded. A step = one checkpoint
@@ -14,8 +21,14 @@ run emits BOTH lines:
   a step = one 1M-row probe batch.
 --workload q3 selects the TPC-H-q3-stream pipeline (configs[4]).
 
-Parity gate: before timing, a small q7 run is compared row-for-row
+Parity gate (--full): before timing, a small q7 run is compared row-for-row
 (multiset per epoch) against the CPU oracle; a mismatch aborts the bench.
+
+--dump-outputs DIR writes the group states the LAST timed q7 step left
+behind (window key, max(price), count — the rows that step emitted as its
+U+ change stream) as DIR/q7_{window,max_price,count}.npy, float64, sorted
+by window. Inputs are seeded, so two builds run with the same arguments
+must write identical files.
 
 Multi-GPU (--gpus N under torchrun): weak scaling, rank-local window key
 ranges (the upstream vnode exchange has already routed keys by window —
@@ -57,6 +70,10 @@ WINDOW_US = 10_000_000   # 10s tumble (q7)
 Q7_BYTES_PER_ROW = 16.0
 Q7_TRAFFIC_B_PER_ROW = (2 * 134_747 + 562) * 1024 / (EPOCH_BATCHES * CHUNK_ROWS * CHUNKS_PER_BATCH)
 HBM_PEAK_GBS = 8000.0  # spec peak (MI355X_MICROARCH.md)
+# step bounds of the join workloads inside the multi-workload run (see main):
+# the largest all-workload run on record (profiles/r02_final2_bench_long.json)
+SIDE_MAX_STEPS = 500
+SIDE_MAX_WARMUP = 25
 
 
 def make_q7_chunk(ffi, rng, n, window_base, n_windows):
@@ -69,6 +86,21 @@ def make_q7_chunk(ffi, rng, n, window_base, n_windows):
         [w, price],
         [np.ones(n, np.uint8), np.ones(n, np.uint8)],
     )
+
+
+def make_q7_epoch(rng, window_base, windows_per_epoch):
+    """The (window key, price) columns of one whole q7 epoch step:
+    EPOCH_BATCHES 1M-row batches, each over its own run of windows, so the
+    window column is ascending across the epoch."""
+    batch_rows = CHUNK_ROWS * CHUNKS_PER_BATCH
+    w_all, p_all = [], []
+    for b in range(EPOCH_BATCHES):
+        base = window_base + b * windows_per_epoch * WINDOW_US
+        w_all.append(base +
+                     np.sort(rng.integers(0, windows_per_epoch,
+                                          batch_rows)) * WINDOW_US)
+        p_all.append(rng.integers(1, 10**7, batch_rows))
+    return np.concatenate(w_all), np.concatenate(p_all)
 
 
 def parity_gate(ffi, gpu_lib, rng):
@@ -157,11 +189,21 @@ def main():
     ap.add_argument("--barrier-every", type=int, default=16)
     ap.add_argument("--windows-per-epoch", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline q7 figure: "
+                         "the oracle parity gate, the q7 full-plan and q8 "
+                         "workloads, the checkpoint-inclusive q7 segment and "
+                         "the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed q7 steps, write the group states "
+                         "the last timed step produced to DIR/<name>.npy")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
     ap.add_argument("--workload",
                     choices=["all", "q7", "q7pipe", "q8", "q3"],
-                    default="all",
-                    help="all (default) = the BASELINE metric 'q7+q8': one "
+                    default=None,
+                    help="default: q7, the headline (all with --full). all = "
+                         "the BASELINE metric 'q7+q8': one "
                          "run emits the q7 line then the q8 line. q7 = "
                          "windowed hash-agg only (configs[1]); q8 = "
                          "stream-stream hash-join, 10M-key build side "
@@ -174,12 +216,19 @@ def main():
                          "(the reference's HashDataDispatcher hop, SURVEY "
                          "§8e). auto = on when WORLD_SIZE > 1")
     args = ap.parse_args()
+    if args.workload is None:
+        args.workload = "all" if args.full else "q7"
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", str(local_rank))
+    if args.dump_outputs is not None and (
+            args.workload not in ("all", "q7") or world > 1
+            or args.exchange == "on"):
+        ap.error("--dump-outputs covers the single-GPU q7 workload without "
+                 "the exchange hop")
 
     dist = None
     if world > 1:
@@ -227,19 +276,31 @@ def main():
 
     rng = np.random.default_rng(args.seed + rank)
 
-    # ---- parity gate (rank 0 only; cheap) ----
-    if rank == 0:
+    # ---- parity gate (rank 0 only; loads the CPU oracle) ----
+    if args.full and rank == 0:
         parity_gate(ffi, gpu_lib, np.random.default_rng(99))
+
+    # In the "all" run --steps/--warmup are sized for the q7 headline, whose
+    # state does not grow. The join workloads that ride along KEEP every
+    # probe row (1M join-state rows per step, preallocated from the step
+    # count), so a q7-sized count of thousands of steps exceeds HBM: they run
+    # at most SIDE_MAX_STEPS/SIDE_MAX_WARMUP and report the count they ran.
+    # Selected on their own (--workload q7pipe/q8) they take --steps as given.
+    side = args
+    if args.workload == "all":
+        side = argparse.Namespace(**vars(args))
+        side.steps = min(args.steps, SIDE_MAX_STEPS)
+        side.warmup = min(args.warmup, SIDE_MAX_WARMUP)
 
     try:
         if args.workload in ("all", "q7"):
             bench_q7(args, ffi, gpu_lib, rng, rank, world, dist)
         if args.workload in ("all", "q7pipe"):
-            bench_q7pipe(args, ffi, gpu_lib,
+            bench_q7pipe(side, ffi, gpu_lib,
                          np.random.default_rng(args.seed + rank + 7),
                          rank, world, dist)
         if args.workload in ("all", "q8"):
-            bench_q8(args, ffi, gpu_lib, np.random.default_rng(args.seed + rank),
+            bench_q8(side, ffi, gpu_lib, np.random.default_rng(args.seed + rank),
                      rank, world, dist)
         if args.workload == "q3":
             bench_q3(args, ffi, gpu_lib, rng, rank, world, dist)
@@ -296,17 +357,11 @@ def bench_q7(args, ffi, gpu_lib, rng, rank, world, dist):
     else:
         # one contiguous 16-step region: the engine buffers an epoch's chunks
         # and applies them as ONE launch before each checkpoint flush
-        w_all, p_all = [], []
-        for b in range(n_batches):
-            base = window_base + b * args.windows_per_epoch * WINDOW_US
-            w_all.append(base +
-                         np.sort(rng.integers(0, args.windows_per_epoch,
-                                              batch_rows)) * WINDOW_US)
-            p_all.append(rng.integers(1, 10**7, batch_rows))
+        w_all, p_all = make_q7_epoch(rng, window_base, args.windows_per_epoch)
         total = n_batches * batch_rows
         giant_c = ffi.Chunk(
             [T_I64, T_I64], np.zeros(total, np.uint8),
-            [np.concatenate(w_all), np.concatenate(p_all)],
+            [w_all, p_all],
             [np.ones(total, np.uint8), np.ones(total, np.uint8)])
         cc = giant_c.to_c()
         giant = L.rw_agg_bench_preload(agg.h, ctypes.byref(cc))
@@ -373,8 +428,11 @@ def bench_q7(args, ffi, gpu_lib, rng, rank, world, dist):
     # epoch cost — apply + host-marshalling flush + device→host spill drain
     # (rw_agg_checkpoint_drain), the preserved-checkpoint path the north
     # star requires as a measured number ----
+    if args.dump_outputs is not None:
+        dump_q7_outputs(args.dump_outputs, ffi, gpu_lib, agg, giant)
+
     ckpt = None
-    if rank == 0 and world == 1 and not use_exchange:
+    if args.full and rank == 0 and world == 1 and not use_exchange:
         L.rw_agg_checkpoint_drain.restype = ctypes.c_int
         L.rw_agg_checkpoint_drain.argtypes = [
             ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
@@ -462,11 +520,54 @@ def bench_q7(args, ffi, gpu_lib, rng, rank, world, dist):
             "checkpoint": ckpt,
             "cpu_baseline": None,
         }
-        if not args.skip_cpu_baseline and world == 1:
+        if args.full and not args.skip_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(ffi, np.random.default_rng(5))
         print(json.dumps(result), flush=True)
 
     agg.close()
+
+
+def dump_q7_outputs(out_dir, ffi, gpu_lib, agg, giant):
+    """Write what the last timed step computed. The timed path keeps its
+    emission device-resident (rw_agg_flush_launch: change inference + prev
+    update in HBM, cursor reset, no host copy), so the rows are read back
+    through the host-marshalling surface: one further UNTIMED epoch over the
+    same region, flushed with rw_hash_agg_flush. Its U- rows retract exactly
+    the (window, max, count) records the last timed flush emitted as U+ —
+    they are that step's output, row for row."""
+    L = gpu_lib.lib
+    rc = L.rw_agg_bench_apply(agg.h, giant)
+    assert rc == 0, gpu_lib.last_error()
+    agg.flush(1 << 40)
+    chunks = agg.poll_all()
+    # the host flush also stages spill records; release them
+    L.rw_agg_checkpoint_drain.restype = ctypes.c_int
+    L.rw_agg_checkpoint_drain.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
+        ctypes.POINTER(ctypes.c_uint64)]
+    L.rw_spill_free.argtypes = [ctypes.POINTER(ctypes.c_uint8)]
+    buf = ctypes.POINTER(ctypes.c_uint8)()
+    ln = ctypes.c_uint64()
+    rc = L.rw_agg_checkpoint_drain(agg.h, ctypes.byref(buf), ctypes.byref(ln))
+    assert rc == 0, gpu_lib.last_error()
+    L.rw_spill_free(buf)
+
+    cols = [[], [], []]
+    for c in chunks:
+        sel = c.ops == ffi.OP_UPDATE_DELETE
+        if c.vis is not None:
+            sel &= c.vis != 0
+        for i in range(3):
+            assert c.valids[i][sel].all(), "NULL in a q7 output column"
+            cols[i].append(c.cols[i][sel])
+    cols = [np.concatenate(c) if c else np.array([], np.int64) for c in cols]
+    assert len(cols[0]), "last timed step left no group state to read back"
+    order = np.argsort(cols[0], kind="stable")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, col in zip(("q7_window", "q7_max_price", "q7_count"), cols):
+        # window keys, prices and counts all stay far below 2^53: exact
+        np.save(os.path.join(out_dir, name + ".npy"),
+                col[order].astype(np.float64))
 
 
 class ExchangeCtx:
@@ -917,7 +1018,7 @@ def bench_q8(args, ffi, gpu_lib, rng, rank, world, dist):
             },
             "cpu_baseline": None,
         }
-        if not args.skip_cpu_baseline and world == 1:
+        if args.full and not args.skip_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline_q8(ffi, np.random.default_rng(5))
         print(json.dumps(result))
     j.close()
