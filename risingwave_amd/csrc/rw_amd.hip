@@ -705,6 +705,7 @@ struct AggTableDev {
     uint32_t* dirty_flag;
     uint32_t* dirty_list;
     uint32_t* counters; // [0]=dirty_count [1]=out_cursor [2]=overflow flag
+                        // [3]=flush arrival ticket (0 outside a flush)
     // flush output buffers (records of width gk+calls)
     long long* out_vals;
     uint8_t* out_nulls;
@@ -1189,11 +1190,25 @@ __device__ __forceinline__ void dense_load(const AggBatch& b,
 // u32 beside the scan instead of an i64 inside it (halves the scan's
 // cross-lane traffic for q7's [max, count] shape and frees the VGPRs the
 // count column held). CS == -1 is the generic path, unchanged.
+//
+// SPAN: each wave owns `span_tiles` ADJACENT 64xRPL-row tiles instead of
+// grid-stride ones, and carries an open run across them. q7 keys arrive in
+// runs far longer than a tile, so nearly every tile holds one key: such a
+// uniform tile (every row in range, every key equal to the tile's first —
+// RPL compares and one vote) folds into per-lane partials in registers
+// with no scan, no table probe and no atomics. The carry is wave-reduced
+// and committed (by lane 0, through the same `commit`) only when a tile
+// with another key or a non-uniform tile arrives, or the span ends; a
+// non-uniform tile then takes the segmented-scan path unchanged. All
+// combiners are commutative and associative on i64 (wrapping add
+// included), so the table state after the launch is bit-identical.
 template <int n_calls, int RPL = 4, bool PF = false, bool NT = false,
-          int CS = -1>
+          int CS = -1, bool SPAN = false>
 __device__ __forceinline__ void agg_apply_dense4_body(
         const AggBatch& b, const AggTableDev& t, AggCallDev c0, AggCallDev c1,
-        AggCallDev c2, AggCallDev c3, uint32_t r0, uint32_t r1) {
+        AggCallDev c2, AggCallDev c3, uint32_t r0, uint32_t r1,
+        uint32_t span_tiles = 0) {
+    static_assert(!(SPAN && PF), "span mapping has no prefetch variant");
     AggCallDev calls[4] = {c0, c1, c2, c3};
     int lane = threadIdx.x & 63;
     size_t cap = (size_t)t.cap_mask + 1;
@@ -1258,16 +1273,88 @@ __device__ __forceinline__ void agg_apply_dense4_body(
     };
 
     uint32_t base = r0 + (blockIdx.x * blockDim.x + threadIdx.x) * RPL;
+    if (SPAN) {
+        // wave-uniform: this wave's tiles are [first, first + iters)
+        const uint32_t tile_rows = 64 * RPL;
+        uint32_t total_tiles = (r1 - r0 + tile_rows - 1) / tile_rows;
+        uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)(threadIdx.x >> 6));
+        uint32_t first = (blockIdx.x * (blockDim.x >> 6) + wave) * span_tiles;
+        iters = first >= total_tiles ? 0
+                : total_tiles - first < span_tiles ? total_tiles - first
+                                                   : span_tiles;
+        base = r0 + first * tile_rows + lane * RPL;
+        stride_rows = tile_rows;
+    }
+    // the carried run (SPAN): key and length are wave-uniform, the value
+    // calls are per-lane partials until the commit reduces them
+    bool have_carry = false;
+    long long carry_key = 0;
+    uint32_t carry_n = 0;
+    long long carry_v[n_calls];
     bool act[RPL];
     long long k[RPL];
     long long cv[RPL][n_calls]; // [row][call]
     if (PF && iters) dense_load<n_calls, RPL, NT, CS>(b, calls, base, r1, act, k, cv);
-    for (uint32_t it = 0; it < iters; it++) {
+    // SPAN runs one extra, data-less trip that commits the last carry, so
+    // the carry commit is inlined once
+    for (uint32_t it = 0; it < iters + (SPAN ? 1u : 0u); it++) {
         uint32_t rb = base + it * stride_rows;
         bool act2[RPL];
         long long k2[RPL];
         long long cv2[RPL][n_calls];
-        if (PF) {
+        if (SPAN) {
+            const bool last = it == iters;
+            bool uni = false;
+            long long k0 = 0;
+            if (!last) {
+                dense_load<n_calls, RPL, NT, CS>(b, calls, rb, r1, act, k, cv);
+                // lane 0's first key, held in scalar registers
+                k0 = (long long)(((unsigned long long)(uint32_t)
+                                      __builtin_amdgcn_readfirstlane(
+                                          (int)((unsigned long long)k[0] >> 32))
+                                  << 32) |
+                                 (uint32_t)__builtin_amdgcn_readfirstlane(
+                                     (int)(unsigned long long)k[0]));
+                bool mine = true;
+#pragma unroll
+                for (int r = 0; r < RPL; r++) mine = mine && act[r] && k[r] == k0;
+                uni = __ballot(mine) == ~0ULL;
+            }
+            if (have_carry && !(uni && k0 == carry_key)) {
+                long long tot[n_calls];
+                _Pragma("unroll") for (int ci = 0; ci < n_calls; ci++) {
+                    if (ci == CS) continue;
+                    long long v = carry_v[ci];
+                    for (int d = 32; d >= 1; d >>= 1)
+                        v = agg4_comb(calls[ci].kind, v, __shfl_xor(v, d));
+                    tot[ci] = v;
+                }
+                if (lane == 0) commit(carry_key, tot, carry_n);
+                have_carry = false;
+            }
+            if (last) break;
+            if (uni) {
+                if (!have_carry) {
+                    have_carry = true;
+                    carry_key = k0;
+                    carry_n = 0;
+                    _Pragma("unroll") for (int ci = 0; ci < n_calls; ci++) {
+                        if (ci == CS) continue;
+                        carry_v[ci] = agg4_identity(calls[ci].kind);
+                    }
+                }
+                _Pragma("unroll") for (int ci = 0; ci < n_calls; ci++) {
+                    if (ci == CS) continue;
+#pragma unroll
+                    for (int r = 0; r < RPL; r++)
+                        carry_v[ci] =
+                            agg4_comb(calls[ci].kind, carry_v[ci], cv[r][ci]);
+                }
+                carry_n += 64 * RPL;
+                continue;
+            }
+        } else if (PF) {
             // double-buffered prefetch: next tile's loads issue before this
             // tile's scan/commit chain, hiding the HBM round-trip
             if (it + 1 < iters)
@@ -1450,6 +1537,16 @@ __global__ __launch_bounds__(256, 8) void agg_apply_dense4_kernel_w8(
         AggCallDev c3, uint32_t r0, uint32_t r1) {
     agg_apply_dense4_body<n_calls, RPL, false, NT, CS>(b, t, c0, c1, c2, c3, r0,
                                                        r1);
+}
+
+// The same with the run-carrying span mapping (see agg_apply_dense4_body):
+// the launch gives each wave `span_tiles` adjacent tiles.
+template <int n_calls, int CS>
+__global__ __launch_bounds__(256, 8) void agg_apply_dense4_kernel_span(
+        AggBatch b, AggTableDev t, AggCallDev c0, AggCallDev c1, AggCallDev c2,
+        AggCallDev c3, uint32_t r0, uint32_t r1, uint32_t span_tiles) {
+    agg_apply_dense4_body<n_calls, 4, false, false, CS, true>(
+        b, t, c0, c1, c2, c3, r0, r1, span_tiles);
 }
 
 // agg_flush: flush_data's emit-on-update branch (hash_agg.rs:475-501) +
@@ -1644,6 +1741,168 @@ __global__ void agg_flush_kernel(AggTableDev t, int KW, int n_calls,
                 t.prev[(size_t)ci * cap + slot] = curr[ci];
                 if (t.prev2) t.prev2[(size_t)ci * cap + slot] = curr2[ci];
                 t.prev_null[(size_t)ci * cap + slot] = curr_null[ci];
+            }
+        }
+    }
+}
+
+// agg_flush_fast: agg_flush_kernel for executors whose calls all keep plain
+// value states (no decimal, no materialized-input call) — q7, q7pipe, q3.
+// Same semantics, restructured around what the generic kernel pays for at
+// a ~1K-slot flush:
+//  - <KW, NC> are compile-time and the call kinds arrive packed one per
+//    byte, so every per-slot array is fully unrolled into registers (no
+//    scratch; the generic kernel indexes its arrays at run time);
+//  - all of a slot's state loads are issued together after the dirty_list
+//    load and the decision is taken afterwards (dirty_list → state → stores:
+//    three dependent round trips);
+//  - one cursor atomic per wave: lanes count their 0/1/2 rows, ballots give
+//    the prefix, lane 0 reserves the wave's rows, a U−/U+ pair stays
+//    adjacent;
+//  - a block without work leaves after reading the dirty count;
+//  - fused_reset: the stream-ordered flush needs counters[0..1] zeroed
+//    after the last slot is handled. Every block that had work draws an
+//    arrival ticket (counters[3]) after its loop; the block drawing the last
+//    one writes the zeros, the ticket included. A block reads the dirty
+//    count before it draws, so the zeros cannot land before a working
+//    block has read it; a block that reads 0 afterwards had no work anyway.
+//    Nothing waits on another block. counters[2] (overflow) stays sticky.
+template <int KW, int NC>
+__global__ __launch_bounds__(256) void agg_flush_fast_kernel(
+        AggTableDev t, int row_count_index, uint32_t kinds, int fused_reset) {
+    const uint32_t n_dirty = __atomic_load_n(&t.counters[0], __ATOMIC_RELAXED);
+    const uint32_t block0 = blockIdx.x * 256u;
+    if (block0 >= n_dirty) return;
+    const uint32_t stride = gridDim.x * 256u;
+    const size_t cap = (size_t)t.cap_mask + 1;
+    constexpr int width = KW + NC;
+    const int lane = threadIdx.x & 63;
+    const uint64_t lanes_below = (1ull << lane) - 1;
+    for (uint32_t i0 = block0; i0 < n_dirty; i0 += stride) {
+        const uint32_t i = i0 + threadIdx.x;
+        uint32_t slot = 0;
+        long long curr[NC], prevv[NC];
+        uint8_t curr_null[NC], prevn[NC];
+        int64_t key[KW];
+        uint32_t knull = 0;
+        int change = 0; // 0 none, 1 insert, 2 delete, 3 update
+        if (i < n_dirty) {
+            slot = t.dirty_list[i];
+            long long a[NC];
+            uint8_t h[NC];
+#pragma unroll
+            for (int ci = 0; ci < NC; ci++) {
+                a[ci] = t.acc[(size_t)ci * cap + slot];
+                h[ci] = t.has[(size_t)ci * cap + slot];
+                prevv[ci] = t.prev[(size_t)ci * cap + slot];
+                prevn[ci] = t.prev_null[(size_t)ci * cap + slot];
+            }
+            const uint8_t hp = t.has_prev[slot];
+#pragma unroll
+            for (int k = 0; k < KW; k++) key[k] = t.keys[(size_t)slot * KW + k];
+            knull = t.key_nulls[slot];
+            // row_count_of clamp (agg_group.rs:63-75); prev/prev_null hold
+            // no meaningful value until has_prev is set
+            long long rc = 0, prc = 0;
+#pragma unroll
+            for (int ci = 0; ci < NC; ci++)
+                if (ci == row_count_index) {
+                    rc = a[ci];
+                    prc = prevv[ci];
+                }
+            if (rc < 0) rc = 0;
+            const long long prev_rc = (hp && prc > 0) ? prc : 0;
+            bool eq = true;
+#pragma unroll
+            for (int ci = 0; ci < NC; ci++) {
+                const uint32_t kind = (kinds >> (8 * ci)) & 0xffu;
+                const bool never_null = kind == RW_AGG_COUNT_STAR ||
+                                        kind == RW_AGG_COUNT ||
+                                        kind == RW_AGG_SUM0;
+                curr[ci] = a[ci];
+                curr_null[ci] = never_null ? 0 : !h[ci];
+                eq = eq && prevn[ci] == curr_null[ci] &&
+                     (prevn[ci] || prevv[ci] == curr[ci]);
+            }
+            // infer_change_type (agg_group.rs:138-163)
+            if (prev_rc == 0 && rc == 0) change = 0;
+            else if (prev_rc == 0) change = 1;
+            else if (rc == 0) change = 2;
+            else change = eq ? 0 : 3;
+            if (rc == 0) {
+                // reset value states (agg_state.rs:149-155)
+#pragma unroll
+                for (int ci = 0; ci < NC; ci++) {
+                    const uint32_t kind = (kinds >> (8 * ci)) & 0xffu;
+                    t.acc[(size_t)ci * cap + slot] =
+                        kind == RW_AGG_MIN ? INT64_MAX
+                        : kind == RW_AGG_MAX ? INT64_MIN : 0;
+                    t.has[(size_t)ci * cap + slot] = 0;
+                }
+            }
+            t.dirty_flag[slot] = 0;
+        }
+        const int n_out = change == 3 ? 2 : (change ? 1 : 0);
+        const uint64_t b1 = __ballot(n_out >= 1);
+        const uint64_t b2 = __ballot(n_out == 2);
+        const uint32_t wave_rows = __popcll(b1) + __popcll(b2);
+        if (wave_rows) { // wave-uniform
+            uint32_t wbase = 0;
+            if (lane == 0) wbase = atomicAdd(&t.counters[1], wave_rows);
+            wbase = __shfl(wbase, 0);
+            const uint32_t orow = wbase + __popcll(b1 & lanes_below) +
+                                  __popcll(b2 & lanes_below);
+            if (n_out && orow + n_out > t.out_capacity) {
+                atomicExch(&t.counters[2], 2u); // output overflow
+            } else if (n_out) {
+                auto write_row = [&](uint32_t r, uint8_t op,
+                                     const long long (&vals)[NC],
+                                     const uint8_t (&nulls)[NC]) {
+                    t.out_ops[r] = op;
+                    long long* ov = t.out_vals + (size_t)r * width;
+                    uint8_t* on = t.out_nulls + (size_t)r * width;
+#pragma unroll
+                    for (int k = 0; k < KW; k++) {
+                        ov[k] = key[k];
+                        on[k] = (knull >> k) & 1;
+                    }
+#pragma unroll
+                    for (int ci = 0; ci < NC; ci++) {
+                        ov[KW + ci] = vals[ci];
+                        on[KW + ci] = nulls[ci];
+                    }
+                };
+                if (change == 1) {
+                    write_row(orow, RW_OP_INSERT, curr, curr_null);
+                } else if (change == 2) {
+                    write_row(orow, RW_OP_DELETE, prevv, prevn);
+                } else {
+                    write_row(orow, RW_OP_UPDATE_DELETE, prevv, prevn);
+                    write_row(orow + 1, RW_OP_UPDATE_INSERT, curr, curr_null);
+                }
+                // prev := curr (or cleared on delete) — agg_group.rs:571-607
+                if (change == 2) {
+                    t.has_prev[slot] = 0;
+                } else {
+                    t.has_prev[slot] = 1;
+#pragma unroll
+                    for (int ci = 0; ci < NC; ci++) {
+                        t.prev[(size_t)ci * cap + slot] = curr[ci];
+                        t.prev_null[(size_t)ci * cap + slot] = curr_null[ci];
+                    }
+                }
+            }
+        }
+    }
+    if (fused_reset) {
+        __syncthreads(); // block-uniform: every thread ran the same trip count
+        if (threadIdx.x == 0) {
+            uint32_t working = (n_dirty + 255u) / 256u;
+            if (working > gridDim.x) working = gridDim.x;
+            if (atomicAdd(&t.counters[3], 1u) == working - 1) {
+                atomicExch(&t.counters[0], 0u); // dirty count
+                atomicExch(&t.counters[1], 0u); // out cursor
+                atomicExch(&t.counters[3], 0u); // ticket
             }
         }
     }
@@ -1909,6 +2168,17 @@ struct HashAgg {
         return (int)(blocks ? blocks : 1);
     }
 
+    // Tiles (256 rows) per wave for the dense kernel's span mapping: the
+    // fewest with which the capped grid covers the rows. Launches of up to
+    // 2M rows keep one tile per wave, and with it all their parallelism;
+    // a 16.7M-row epoch at the 2048-block cap gets 8.
+    static uint32_t span_tiles_for(uint32_t rows, int grid) {
+        uint32_t tiles = (rows + 255) / 256;
+        uint32_t waves = (uint32_t)grid * 4;
+        return (tiles + waves - 1) / waves;
+    }
+    uint32_t span_tiles_override = 0; // rw_agg_debug_set_span_tiles
+
     AggCallDev cd(int i) const {
         if (i < n_calls) {
             int8_t mord = 0, dord = 0;
@@ -2033,8 +2303,8 @@ struct HashAgg {
         HIP_TRY(hipMalloc(&t.dirty_flag, cap * 4));
         HIP_TRY(hipMemset(t.dirty_flag, 0, cap * 4));
         HIP_TRY(hipMalloc(&t.dirty_list, cap * 4));
-        HIP_TRY(hipMalloc(&t.counters, 3 * 4));
-        HIP_TRY(hipMemset(t.counters, 0, 3 * 4));
+        HIP_TRY(hipMalloc(&t.counters, 4 * 4));
+        HIP_TRY(hipMemset(t.counters, 0, 4 * 4));
         t.out_capacity = 1u << 22;
         HIP_TRY(hipMalloc(&t.out_vals, (size_t)t.out_capacity * out_width * 8));
         HIP_TRY(hipMalloc(&t.out_nulls, (size_t)t.out_capacity * out_width));
@@ -2230,7 +2500,31 @@ struct HashAgg {
                 if (cd(ci).arg < 0 && cd(ci).kind == RW_AGG_COUNT_STAR) cs = ci;
             if (cs_en && cs >= 0 && rpl == 4 && !pf && !nt) {
                 bool cs_w8 = w8_env != 0; // default ON here
-                #define RW_DCS(nc, csv)                                        \
+                // SPAN: contiguous per-wave spans with a carried run
+                // (A/B via RW_AGG_SPAN=0: the grid-stride mapping)
+                static int span_en = [] {
+                    const char* e = getenv("RW_AGG_SPAN");
+                    return !(e && *e == '0');
+                }();
+                if (cs_w8 && span_en) {
+                    uint32_t tiles = (r1 - r0 + 255) / 256;
+                    uint32_t st = span_tiles_override
+                                      ? span_tiles_override
+                                      : span_tiles_for(r1 - r0, grid);
+                    uint32_t waves = (tiles + st - 1) / st;
+                    int sgrid = (int)((waves + 3) / 4);
+                    #define RW_DSP(nc, csv)                                    \
+                        agg_apply_dense4_kernel_span<nc, csv>                  \
+                            <<<sgrid, 256, 0, stream>>>(b, t, a0, a1, a2, a3,  \
+                                                        r0, r1, st)
+                    switch (n_calls * 8 + cs) {
+                        case 1 * 8 + 0: RW_DSP(1, 0); return;
+                        case 2 * 8 + 0: RW_DSP(2, 0); return;
+                        case 2 * 8 + 1: RW_DSP(2, 1); return;
+                    }
+                    #undef RW_DSP
+                }
+                #define RW_DCS(nc, csv)                                       \
                     agg_apply_dense4_kernel<nc, 4, false, false, csv>          \
                         <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1)
                 #define RW_DCS8(nc, csv)                                       \
@@ -2617,11 +2911,54 @@ struct HashAgg {
 
     // sync the stream, read the dirty count, and size the output buffers for
     // the worst case (2 rows per dirty group) ahead of the flush launch
-    int presize_flush_out() {
+    int presize_flush_out(uint32_t* n_dirty = nullptr) {
         HIP_TRY(hipStreamSynchronize(stream));
         uint32_t nd = 0;
         HIP_TRY(hipMemcpy(&nd, t.counters, 4, hipMemcpyDeviceToHost));
+        if (n_dirty) *n_dirty = nd;
         return ensure_out_capacity((uint64_t)nd * 2);
+    }
+
+    // The one place the change-inference flush is launched from.
+    // `n_dirty` is the exact dirty count where the caller has just read it
+    // (the host-synchronous paths), or -1 on the stream-ordered path, which
+    // also wants counters[0..1] zeroed behind the flush (`stream_reset`).
+    // Value-state executors take agg_flush_fast_kernel: the grid is sized
+    // to the count when it is known; unknown, 512 blocks cover 128K slots
+    // per grid-stride pass, blocks past the dirty count exit on their first
+    // load, and at most 512 blocks ever draw a reset ticket. Decimal and
+    // materialized-input executors, or RW_AGG_FLUSH_FAST=0 (A/B), keep the
+    // generic kernel at its fixed grid with the separate reset launch.
+    void launch_flush(long long n_dirty, bool stream_reset) {
+        static int fast_en = [] {
+            const char* e = getenv("RW_AGG_FLUSH_FAST");
+            return !(e && *e == '0');
+        }();
+        if (fast_en && n_dec == 0 && n_minput == 0) {
+            if (n_dirty == 0) return; // counters already read back as idle
+            int grid = n_dirty < 0 ? 512 : grid_for((uint32_t)n_dirty);
+            uint32_t kinds = 0;
+            for (int ci = 0; ci < n_calls; ci++)
+                kinds |= (uint32_t)calls[ci].kind << (8 * ci);
+            #define RW_FF(kw, nc)                                              \
+                case kw * 8 + nc:                                              \
+                    agg_flush_fast_kernel<kw, nc><<<grid, 256, 0, stream>>>(   \
+                        t, (int)desc.row_count_index, kinds,                   \
+                        stream_reset ? 1 : 0);                                 \
+                    return;
+            switch (KW * 8 + n_calls) {
+                RW_FF(1, 1) RW_FF(1, 2) RW_FF(1, 3) RW_FF(1, 4)
+                RW_FF(2, 1) RW_FF(2, 2) RW_FF(2, 3) RW_FF(2, 4)
+                RW_FF(3, 1) RW_FF(3, 2) RW_FF(3, 3) RW_FF(3, 4)
+                RW_FF(4, 1) RW_FF(4, 2) RW_FF(4, 3) RW_FF(4, 4)
+            }
+            #undef RW_FF
+        }
+        agg_flush_kernel<<<2048, 256, 0, stream>>>(
+            t, KW, n_calls, (int)desc.row_count_index, cd(0), cd(1), cd(2),
+            cd(3));
+        if (stream_reset)
+            agg_counters_reset_kernel<<<1, 1, 0, stream>>>(t.counters);
     }
 
     int flush(uint64_t) {
@@ -2629,7 +2966,8 @@ struct HashAgg {
             int rce = epoch_apply();
             if (rce != RW_OK) return rce;
         }
-        int rcp = presize_flush_out();
+        uint32_t n_dirty = 0;
+        int rcp = presize_flush_out(&n_dirty);
         if (rcp != RW_OK) return rcp;
         if (eowc) {
             // EOWC barrier (hash_agg.rs:429-474): nothing is EMITTED until a
@@ -2726,9 +3064,7 @@ struct HashAgg {
             HIP_TRY(hipMemset(t.counters, 0, 12));
             return RW_OK;
         }
-        agg_flush_kernel<<<2048, 256, 0, stream>>>(t, KW, n_calls,
-                                                   (int)desc.row_count_index, cd(0),
-                                                   cd(1), cd(2), cd(3));
+        launch_flush(n_dirty, false);
         HIP_TRY(hipStreamSynchronize(stream));
         int rc = check_overflow();
         if (rc != RW_OK) return rc;
@@ -3759,10 +4095,9 @@ int rw_agg_apply_payload(void* h, const uint8_t* payload,
 long long rw_agg_flush_device(void* h, uint64_t epoch) {
     auto* agg = (HashAgg*)h;
     (void)epoch;
-    if (agg->presize_flush_out() != RW_OK) return -1;
-    agg_flush_kernel<<<2048, 256, 0, agg->stream>>>(
-        agg->t, agg->KW, agg->n_calls, (int)agg->desc.row_count_index,
-        agg->cd(0), agg->cd(1), agg->cd(2), agg->cd(3));
+    uint32_t n_dirty = 0;
+    if (agg->presize_flush_out(&n_dirty) != RW_OK) return -1;
+    agg->launch_flush(n_dirty, false);
     if (hipStreamSynchronize(agg->stream) != hipSuccess) return -1;
     uint32_t ctr[3];
     if (hipMemcpy(ctr, agg->t.counters, 12, hipMemcpyDeviceToHost) != hipSuccess)
@@ -3781,17 +4116,16 @@ __global__ void agg_counters_reset_kernel(uint32_t* counters) {
     counters[1] = 0; // out cursor
 }
 
-// fully async flush: the change-inference kernel + counter reset run
-// stream-ordered with no host round-trip; the overflow flag (counters[2])
-// is left set and surfaces at the next rw_agg_sync. The emitted rows are
-// device-resident for the downstream, as with rw_agg_flush_device.
+// fully async flush: change inference and the counter reset run
+// stream-ordered with no host round-trip (one launch for value-state
+// executors, whose flush kernel resets the counters itself; see
+// HashAgg::launch_flush); the overflow flag (counters[2]) is left set and
+// surfaces at the next rw_agg_sync. The emitted rows are device-resident
+// for the downstream, as with rw_agg_flush_device.
 int rw_agg_flush_launch(void* h, uint64_t epoch) {
     auto* agg = (HashAgg*)h;
     (void)epoch;
-    agg_flush_kernel<<<2048, 256, 0, agg->stream>>>(
-        agg->t, agg->KW, agg->n_calls, (int)agg->desc.row_count_index,
-        agg->cd(0), agg->cd(1), agg->cd(2), agg->cd(3));
-    agg_counters_reset_kernel<<<1, 1, 0, agg->stream>>>(agg->t.counters);
+    agg->launch_flush(-1, true);
     return RW_OK;
 }
 
@@ -3812,6 +4146,14 @@ typedef struct {
     uint64_t dirty_count;
     uint64_t out_cursor;
 } RwAggDebug;
+
+// debug: fix the dense span kernel's tiles-per-wave for this executor (0 =
+// the launch policy, HashAgg::span_tiles_for) — lets tests reach multi-tile
+// spans at small row counts
+int rw_agg_debug_set_span_tiles(void* h, uint32_t n) {
+    ((HashAgg*)h)->span_tiles_override = n;
+    return RW_OK;
+}
 
 int rw_agg_debug_scan(void* h, RwAggDebug* out) {
     auto* agg = (HashAgg*)h;
