@@ -757,7 +757,7 @@ struct AggTableDev {
 template <int KW, int n_calls, bool DENSE>
 __global__ void agg_apply_kernel(AggBatch b, AggTableDev t, AggCallDev c0,
                                  AggCallDev c1, AggCallDev c2, AggCallDev c3,
-                                 int mode, uint32_t r0, uint32_t r1) {
+                                 uint32_t r0, uint32_t r1) {
     AggCallDev calls[4] = {c0, c1, c2, c3};
     uint32_t stride = gridDim.x * blockDim.x;
     uint32_t iters = (r1 - r0 + stride - 1) / stride;
@@ -801,16 +801,7 @@ __global__ void agg_apply_kernel(AggBatch b, AggTableDev t, AggCallDev c0,
         same = same && (pn == nullmask);
         bool prev_active = lane > 0 && ((act_b >> (lane - 1)) & 1);
         bool head = active && !(same && prev_active);
-        if (mode == 2) head = active; // debug: no dedupe, per-lane probe
         uint32_t slot = SLOT_NONE;
-        if (mode == 4) { // debug: loads only (no probe/scan/atomics)
-            long long acc4 = nullmask;
-            for (int i = 0; i < KW; i++) acc4 += kw[i];
-            for (int ci = 0; ci < n_calls; ci++)
-                if (active && calls[ci].arg >= 0) acc4 += b.col_vals[KW + ci][rs];
-            if (acc4 == 0x7fffffffffffffffLL) t.counters[2] = 9;
-            continue;
-        }
         if (head) {
             bool memo_hit = memo_slot != SLOT_NONE && nullmask == memo_null;
             for (int i = 0; i < KW; i++) memo_hit = memo_hit && kw[i] == memo_kw[i];
@@ -982,47 +973,6 @@ __global__ void agg_apply_kernel(AggBatch b, AggTableDev t, AggCallDev c0,
                     break;
             }
         }
-        if (mode == 1) {
-            // debug fallback: per-lane atomics, no wave aggregation
-            if (contributing) {
-                for (int ci = 0; ci < n_calls; ci++) {
-                    if (calls[ci].minput || calls[ci].decimal) continue;
-                    long long* acc = t.acc + (size_t)ci * cap;
-                    uint8_t* has = t.has + (size_t)ci * cap;
-                    switch (calls[ci].kind) {
-                        case RW_AGG_COUNT_STAR:
-                        case RW_AGG_COUNT:
-                            if (v[ci]) atomic_add_i64(&acc[slot], v[ci]);
-                            break;
-                        case RW_AGG_SUM:
-                        case RW_AGG_SUM0:
-                            if (hasmask & (1 << ci)) {
-                                atomic_add_i64(&acc[slot], v[ci]);
-                                if (!has[slot]) has[slot] = 1;
-                            }
-                            break;
-                        case RW_AGG_MIN:
-                            if (hasmask & (1 << ci)) {
-                                atomic_min_i64(&acc[slot], v[ci]);
-                                if (!has[slot]) has[slot] = 1;
-                            }
-                            break;
-                        case RW_AGG_MAX:
-                            if (hasmask & (1 << ci)) {
-                                atomic_max_i64(&acc[slot], v[ci]);
-                                if (!has[slot]) has[slot] = 1;
-                            }
-                            break;
-                    }
-                }
-                if (ld_u32(&t.dirty_flag[slot]) == 0 &&
-                    atomicCAS(&t.dirty_flag[slot], 0u, 1u) == 0u) {
-                    uint32_t i = atomicAdd(&t.counters[0], 1u);
-                    t.dirty_list[i] = slot;
-                }
-            }
-            continue;
-        }
         // segmented inclusive reduction over the runs; the run TAIL issues
         // one atomic per call (order-free combines: +, min, max, OR)
         for (int d = 1; d < 64; d <<= 1) {
@@ -1049,10 +999,6 @@ __global__ void agg_apply_kernel(AggBatch b, AggTableDev t, AggCallDev c0,
         uint64_t cont_b = __ballot(contributing);
         uint64_t ends_after = (heads_b | ~cont_b) >> 1 | (1ULL << 63);
         bool tail = contributing && ((ends_after >> lane) & 1);
-        if (mode == 3) { // debug: skip the tail atomics
-            if (tail && v[0] == 0x7fffffffffffffffLL) t.counters[2] = 9;
-            continue;
-        }
         if (tail) {
             for (int ci = 0; ci < n_calls; ci++) {
                 if (calls[ci].minput || calls[ci].decimal) continue;
@@ -1120,22 +1066,12 @@ __device__ __forceinline__ long long agg4_comb(uint8_t kind, long long a,
     }
 }
 
-template <bool NT>
-__device__ __forceinline__ ulonglong2 ld_b128(const ulonglong2* p) {
-    // NT = nontemporal (streaming) load: the input chunk is read exactly
-    // once per epoch, so bypassing L2 retention leaves the cache to the
-    // state table (A/B via RW_AGG_NT=1).
-    if constexpr (NT) {
-        const unsigned long long* q = (const unsigned long long*)p;
-        ulonglong2 r;
-        r.x = __builtin_nontemporal_load(q);
-        r.y = __builtin_nontemporal_load(q + 1);
-        return r;
-    }
-    return *p;
-}
+// Rows per lane. Measured on MI355X at q7 sizes: 4 → 37.8 G rows/s,
+// 8 → 28.9, 16 → 23.0 — the VGPR cost of wider per-lane tiles outweighs
+// the deeper load pipeline.
+constexpr int RPL = 4;
 
-template <int n_calls, int RPL, bool NT = false, int CS = -1>
+template <int n_calls, int CS>
 __device__ __forceinline__ void dense_load(const AggBatch& b,
                                            const AggCallDev* calls,
                                            uint32_t rb, uint32_t r1, bool* act,
@@ -1147,7 +1083,7 @@ __device__ __forceinline__ void dense_load(const AggBatch& b,
         const ulonglong2* kp = (const ulonglong2*)(b.col_vals[0] + rb);
 #pragma unroll
         for (int h = 0; h < RPL / 2; h++) {
-            ulonglong2 kk = ld_b128<NT>(kp + h);
+            ulonglong2 kk = kp[h];
             k[2 * h] = (long long)kk.x;
             k[2 * h + 1] = (long long)kk.y;
         }
@@ -1163,7 +1099,7 @@ __device__ __forceinline__ void dense_load(const AggBatch& b,
             const ulonglong2* vp = (const ulonglong2*)(b.col_vals[1 + ci] + rb);
 #pragma unroll
             for (int h = 0; h < RPL / 2; h++) {
-                ulonglong2 vv = ld_b128<NT>(vp + h);
+                ulonglong2 vv = vp[h];
                 cv[2 * h][ci] = agg4_unit(calls[ci].kind, (long long)vv.x);
                 cv[2 * h + 1][ci] = agg4_unit(calls[ci].kind, (long long)vv.y);
             }
@@ -1202,13 +1138,11 @@ __device__ __forceinline__ void dense_load(const AggBatch& b,
 // non-uniform tile then takes the segmented-scan path unchanged. All
 // combiners are commutative and associative on i64 (wrapping add
 // included), so the table state after the launch is bit-identical.
-template <int n_calls, int RPL = 4, bool PF = false, bool NT = false,
-          int CS = -1, bool SPAN = false>
+template <int n_calls, int CS = -1, bool SPAN = false>
 __device__ __forceinline__ void agg_apply_dense4_body(
         const AggBatch& b, const AggTableDev& t, AggCallDev c0, AggCallDev c1,
         AggCallDev c2, AggCallDev c3, uint32_t r0, uint32_t r1,
         uint32_t span_tiles = 0) {
-    static_assert(!(SPAN && PF), "span mapping has no prefetch variant");
     AggCallDev calls[4] = {c0, c1, c2, c3};
     int lane = threadIdx.x & 63;
     size_t cap = (size_t)t.cap_mask + 1;
@@ -1295,20 +1229,16 @@ __device__ __forceinline__ void agg_apply_dense4_body(
     bool act[RPL];
     long long k[RPL];
     long long cv[RPL][n_calls]; // [row][call]
-    if (PF && iters) dense_load<n_calls, RPL, NT, CS>(b, calls, base, r1, act, k, cv);
     // SPAN runs one extra, data-less trip that commits the last carry, so
     // the carry commit is inlined once
     for (uint32_t it = 0; it < iters + (SPAN ? 1u : 0u); it++) {
         uint32_t rb = base + it * stride_rows;
-        bool act2[RPL];
-        long long k2[RPL];
-        long long cv2[RPL][n_calls];
         if (SPAN) {
             const bool last = it == iters;
             bool uni = false;
             long long k0 = 0;
             if (!last) {
-                dense_load<n_calls, RPL, NT, CS>(b, calls, rb, r1, act, k, cv);
+                dense_load<n_calls, CS>(b, calls, rb, r1, act, k, cv);
                 // lane 0's first key, held in scalar registers
                 k0 = (long long)(((unsigned long long)(uint32_t)
                                       __builtin_amdgcn_readfirstlane(
@@ -1354,14 +1284,8 @@ __device__ __forceinline__ void agg_apply_dense4_body(
                 carry_n += 64 * RPL;
                 continue;
             }
-        } else if (PF) {
-            // double-buffered prefetch: next tile's loads issue before this
-            // tile's scan/commit chain, hiding the HBM round-trip
-            if (it + 1 < iters)
-                dense_load<n_calls, RPL, NT, CS>(b, calls, rb + stride_rows, r1, act2,
-                                         k2, cv2);
         } else {
-            dense_load<n_calls, RPL, NT, CS>(b, calls, rb, r1, act, k, cv);
+            dense_load<n_calls, CS>(b, calls, rb, r1, act, k, cv);
         }
         // lane-local segments over the RPL rows (inactive rows break runs)
         long long last_key = 0;
@@ -1505,38 +1429,28 @@ __device__ __forceinline__ void agg_apply_dense4_body(
                 // the next lane commits incoming (== this incl) + its prefix
             }
         }
-        if (PF && it + 1 < iters) {
-#pragma unroll
-            for (int r = 0; r < RPL; r++) {
-                act[r] = act2[r];
-                k[r] = k2[r];
-                _Pragma("unroll") for (int ci = 0; ci < n_calls; ci++) {
-                    if (ci == CS) continue;
-                    cv[r][ci] = cv2[r][ci];
-                }
-            }
-        }
     }
 }
 
-template <int n_calls, int RPL = 4, bool PF = false, bool NT = false,
-          int CS = -1>
+// Generic shapes (no count-star carried as run length): grid-stride tiles,
+// no register cap — capping these at 64 VGPRs spilled 8 for +2.5%.
+template <int n_calls>
 __global__ void agg_apply_dense4_kernel(AggBatch b, AggTableDev t, AggCallDev c0,
                                         AggCallDev c1, AggCallDev c2,
                                         AggCallDev c3, uint32_t r0, uint32_t r1) {
-    agg_apply_dense4_body<n_calls, RPL, PF, NT, CS>(b, t, c0, c1, c2, c3, r0, r1);
+    agg_apply_dense4_body<n_calls>(b, t, c0, c1, c2, c3, r0, r1);
 }
 
-// Occupancy variant (measured +2.5% at 71→64 VGPRs even with 8 spilled
-// regs, gpurun_out/q7_w8.json): cap the register budget at 64 VGPRs so 8
-// waves/SIMD are resident instead of the default build's 7 — more
-// latency-hiding on a latency-structured kernel. A/B via RW_AGG_W8=0/1.
-template <int n_calls, int RPL = 4, bool NT = false, int CS = -1>
+// Count-star shapes, grid-stride: cap the register budget at 64 VGPRs so 8
+// waves/SIMD are resident instead of the unbounded build's 7 — more
+// latency-hiding on a latency-structured kernel. Measured 160.3 vs 135.0
+// G rows/s over the unbounded CS build (the launch-bounds contract also
+// changes scheduling, not just the register cap).
+template <int n_calls, int CS>
 __global__ __launch_bounds__(256, 8) void agg_apply_dense4_kernel_w8(
         AggBatch b, AggTableDev t, AggCallDev c0, AggCallDev c1, AggCallDev c2,
         AggCallDev c3, uint32_t r0, uint32_t r1) {
-    agg_apply_dense4_body<n_calls, RPL, false, NT, CS>(b, t, c0, c1, c2, c3, r0,
-                                                       r1);
+    agg_apply_dense4_body<n_calls, CS>(b, t, c0, c1, c2, c3, r0, r1);
 }
 
 // The same with the run-carrying span mapping (see agg_apply_dense4_body):
@@ -1545,8 +1459,8 @@ template <int n_calls, int CS>
 __global__ __launch_bounds__(256, 8) void agg_apply_dense4_kernel_span(
         AggBatch b, AggTableDev t, AggCallDev c0, AggCallDev c1, AggCallDev c2,
         AggCallDev c3, uint32_t r0, uint32_t r1, uint32_t span_tiles) {
-    agg_apply_dense4_body<n_calls, 4, false, false, CS, true>(
-        b, t, c0, c1, c2, c3, r0, r1, span_tiles);
+    agg_apply_dense4_body<n_calls, CS, true>(b, t, c0, c1, c2, c3, r0, r1,
+                                             span_tiles);
 }
 
 // agg_flush: flush_data's emit-on-update branch (hash_agg.rs:475-501) +
@@ -2137,7 +2051,6 @@ struct HashAgg {
     // checkpoint spill buffer (§8f-2): state-table KV deltas, accumulated at
     // flush, drained by rw_agg_checkpoint_drain
     std::vector<uint8_t> spill;
-    int debug_mode = 0; // RW_AGG_DEBUG_MODE: 1 per-lane atomics, 2 no-dedupe
     uint8_t* d_vnode_bitmap = nullptr; // rescale scope (update_vnode_bitmap)
     uint16_t* d_vnode_hop = nullptr;   // q7-pipeline exchange-hop vnodes
     uint32_t d_vnode_hop_cap = 0;
@@ -2194,7 +2107,6 @@ struct HashAgg {
 
     int init(const RwHashAggDesc* d) {
         if (!gpu_ok()) FAIL(RW_E_NOGPU, "risingwave_amd: no GPU visible (product path has no CPU fallback)");
-        if (const char* m = getenv("RW_AGG_DEBUG_MODE")) debug_mode = atoi(m);
         desc = *d;
         eowc = d->emit_on_window_close != 0;
         input_types.assign(d->input_types, d->input_types + d->n_input_cols);
@@ -2456,144 +2368,54 @@ struct HashAgg {
         auto a0 = cd(0), a1 = cd(1), a2 = cd(2), a3 = cd(3);
         if (b.dense && KW == 1 && b.stride == 1 && n_minput == 0 &&
             n_dec == 0 && distinct_slots.empty() &&
-            debug_mode == 0 && ((uintptr_t)(b.col_vals[0] + r0) & 31) == 0 &&
+            ((uintptr_t)(b.col_vals[0] + r0) & 31) == 0 &&
             (r1 - r0) >= 1024) {
-            // rows-per-lane (A/B-selectable via RW_AGG_RPL). Measured on
-            // MI355X at q7 sizes: 4 → 37.8 G rows/s, 8 → 28.9, 16 → 23.0 —
-            // the VGPR cost of wider per-lane tiles outweighs the deeper
-            // load pipeline, so 4 is the default.
-            static int rpl = [] {
-                const char* e = getenv("RW_AGG_RPL");
-                int v = e ? atoi(e) : 4;
-                return (v == 4 || v == 8 || v == 16) ? v : 4;
-            }();
-            // PF: double-buffered prefetch variant (A/B via RW_AGG_PF=1)
-            static int pf = [] {
-                const char* e = getenv("RW_AGG_PF");
-                return e && *e == '1';
-            }();
-            // W8: 8-waves/SIMD register-capped variant. Default ON for the
-            // count-specialized (CS) path — measured 160.3 vs 135.0 G rows/s
-            // over the unbounded CS build (gpurun_out/q7_csw8.json; the
-            // launch-bounds contract also changes scheduling, not just the
-            // register cap). RW_AGG_W8=0 disables, =1 forces it for the
-            // generic path too (there it spills 8 VGPRs and wins only ~2%).
-            static int w8_env = [] {
-                const char* e = getenv("RW_AGG_W8");
-                return e ? (*e == '1' ? 1 : 0) : -1;
-            }();
-            int w8 = w8_env == 1;
-            // NT: nontemporal input loads (A/B via RW_AGG_NT=1)
-            static int nt = [] {
-                const char* e = getenv("RW_AGG_NT");
-                return e && *e == '1';
-            }();
-            int grid = grid_for((r1 - r0 + rpl - 1) / rpl);
+            int grid = grid_for((r1 - r0 + RPL - 1) / RPL);
             // CS: count-star carried as run length beside the scan instead
-            // of an i64 inside it (A/B via RW_AGG_CS=0; default on).
-            static int cs_en = [] {
-                const char* e = getenv("RW_AGG_CS");
-                return !(e && *e == '0');
-            }();
+            // of an i64 inside it
             int cs = -1;
             for (int ci = 0; ci < n_calls && cs < 0; ci++)
                 if (cd(ci).arg < 0 && cd(ci).kind == RW_AGG_COUNT_STAR) cs = ci;
-            if (cs_en && cs >= 0 && rpl == 4 && !pf && !nt) {
-                bool cs_w8 = w8_env != 0; // default ON here
-                // SPAN: contiguous per-wave spans with a carried run
-                // (A/B via RW_AGG_SPAN=0: the grid-stride mapping)
-                static int span_en = [] {
-                    const char* e = getenv("RW_AGG_SPAN");
-                    return !(e && *e == '0');
-                }();
-                if (cs_w8 && span_en) {
-                    uint32_t tiles = (r1 - r0 + 255) / 256;
-                    uint32_t st = span_tiles_override
-                                      ? span_tiles_override
-                                      : span_tiles_for(r1 - r0, grid);
-                    uint32_t waves = (tiles + st - 1) / st;
-                    int sgrid = (int)((waves + 3) / 4);
-                    #define RW_DSP(nc, csv)                                    \
-                        agg_apply_dense4_kernel_span<nc, csv>                  \
-                            <<<sgrid, 256, 0, stream>>>(b, t, a0, a1, a2, a3,  \
-                                                        r0, r1, st)
-                    switch (n_calls * 8 + cs) {
-                        case 1 * 8 + 0: RW_DSP(1, 0); return;
-                        case 2 * 8 + 0: RW_DSP(2, 0); return;
-                        case 2 * 8 + 1: RW_DSP(2, 1); return;
-                    }
-                    #undef RW_DSP
-                }
-                #define RW_DCS(nc, csv)                                       \
-                    agg_apply_dense4_kernel<nc, 4, false, false, csv>          \
-                        <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1)
-                #define RW_DCS8(nc, csv)                                       \
-                    agg_apply_dense4_kernel_w8<nc, 4, false, csv>              \
-                        <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1)
-                switch ((cs_w8 ? 128 : 0) + n_calls * 8 + cs) {
-                    case 1 * 8 + 0: RW_DCS(1, 0); return;
-                    case 2 * 8 + 0: RW_DCS(2, 0); return;
-                    case 2 * 8 + 1: RW_DCS(2, 1); return;
-                    case 128 + 1 * 8 + 0: RW_DCS8(1, 0); return;
-                    case 128 + 2 * 8 + 0: RW_DCS8(2, 0); return;
-                    case 128 + 2 * 8 + 1: RW_DCS8(2, 1); return;
-                }
-                #undef RW_DCS
-                #undef RW_DCS8
-            }
-            if (w8 && rpl == 4) {
-                #define RW_DW8(nc, ntv)                                        \
-                    agg_apply_dense4_kernel_w8<nc, 4, ntv>                     \
-                        <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1)
-                switch (n_calls * 2 + (nt ? 1 : 0)) {
-                    case 1 * 2 + 0: RW_DW8(1, false); return;
-                    case 1 * 2 + 1: RW_DW8(1, true); return;
-                    case 2 * 2 + 0: RW_DW8(2, false); return;
-                    case 2 * 2 + 1: RW_DW8(2, true); return;
-                    case 3 * 2 + 0: RW_DW8(3, false); return;
-                    case 3 * 2 + 1: RW_DW8(3, true); return;
-                    case 4 * 2 + 0: RW_DW8(4, false); return;
-                    case 4 * 2 + 1: RW_DW8(4, true); return;
-                }
-                #undef RW_DW8
-            }
-            if (nt && rpl == 4) {
-                #define RW_DNT(nc)                                             \
-                    agg_apply_dense4_kernel<nc, 4, false, true>                \
-                        <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1)
-                switch (n_calls) {
-                    case 1: RW_DNT(1); return;
-                    case 2: RW_DNT(2); return;
-                    case 3: RW_DNT(3); return;
-                    case 4: RW_DNT(4); return;
-                }
-                #undef RW_DNT
-            }
-            if (pf && rpl == 4) {
-                switch (n_calls) {
-                    case 1: agg_apply_dense4_kernel<1, 4, true><<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1); return;
-                    case 2: agg_apply_dense4_kernel<2, 4, true><<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1); return;
-                    case 3: agg_apply_dense4_kernel<3, 4, true><<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1); return;
-                    case 4: agg_apply_dense4_kernel<4, 4, true><<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, r0, r1); return;
-                }
-            }
-            #define RW_DENSE(nc, rp)                                          \
-                agg_apply_dense4_kernel<nc, rp><<<grid, 256, 0, stream>>>(    \
+            // SPAN: contiguous per-wave spans with a carried run
+            // (A/B via RW_AGG_SPAN=0: the grid-stride mapping)
+            static int span_en = [] {
+                const char* e = getenv("RW_AGG_SPAN");
+                return !(e && *e == '0');
+            }();
+            uint32_t tiles = (r1 - r0 + 64 * RPL - 1) / (64 * RPL);
+            uint32_t st = span_tiles_override ? span_tiles_override
+                                              : span_tiles_for(r1 - r0, grid);
+            uint32_t waves = (tiles + st - 1) / st;
+            int sgrid = (int)((waves + 3) / 4);
+            #define RW_DCS(nc, csv)                                           \
+                do {                                                          \
+                    if (span_en)                                              \
+                        agg_apply_dense4_kernel_span<nc, csv>                 \
+                            <<<sgrid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, \
+                                                        r0, r1, st);          \
+                    else                                                      \
+                        agg_apply_dense4_kernel_w8<nc, csv>                   \
+                            <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3,  \
+                                                       r0, r1);               \
+                } while (0)
+            #define RW_DENSE(nc)                                              \
+                agg_apply_dense4_kernel<nc><<<grid, 256, 0, stream>>>(        \
                     b, t, a0, a1, a2, a3, r0, r1)
-            switch (n_calls * 32 + rpl) {
-                case 1 * 32 + 4: RW_DENSE(1, 4); return;
-                case 1 * 32 + 8: RW_DENSE(1, 8); return;
-                case 1 * 32 + 16: RW_DENSE(1, 16); return;
-                case 2 * 32 + 4: RW_DENSE(2, 4); return;
-                case 2 * 32 + 8: RW_DENSE(2, 8); return;
-                case 2 * 32 + 16: RW_DENSE(2, 16); return;
-                case 3 * 32 + 4: RW_DENSE(3, 4); return;
-                case 3 * 32 + 8: RW_DENSE(3, 8); return;
-                case 3 * 32 + 16: RW_DENSE(3, 16); return;
-                case 4 * 32 + 4: RW_DENSE(4, 4); return;
-                case 4 * 32 + 8: RW_DENSE(4, 8); return;
-                case 4 * 32 + 16: RW_DENSE(4, 16); return;
+            // the count-star shapes of q7 ([count], [max|sum, count] either
+            // way round) have the CS kernels; every other shape, count-star
+            // with 3 or 4 calls included, takes the generic one
+            switch (cs < 0 ? -1 : n_calls * 8 + cs) {
+                case 1 * 8 + 0: RW_DCS(1, 0); return;
+                case 2 * 8 + 0: RW_DCS(2, 0); return;
+                case 2 * 8 + 1: RW_DCS(2, 1); return;
             }
+            switch (n_calls) {
+                case 1: RW_DENSE(1); return;
+                case 2: RW_DENSE(2); return;
+                case 3: RW_DENSE(3); return;
+                case 4: RW_DENSE(4); return;
+            }
+            #undef RW_DCS
             #undef RW_DENSE
         }
         int grid = grid_for(r1 - r0);
@@ -2601,10 +2423,10 @@ struct HashAgg {
             do {                                                              \
                 if (b.dense)                                                  \
                     agg_apply_kernel<kw, nc, true><<<grid, 256, 0, stream>>>( \
-                        b, t, a0, a1, a2, a3, debug_mode, r0, r1);            \
+                        b, t, a0, a1, a2, a3, r0, r1);                        \
                 else                                                          \
                     agg_apply_kernel<kw, nc, false><<<grid, 256, 0, stream>>>(\
-                        b, t, a0, a1, a2, a3, debug_mode, r0, r1);            \
+                        b, t, a0, a1, a2, a3, r0, r1);                        \
             } while (0)
         switch (KW * 8 + n_calls) {
             case 1 * 8 + 1: RW_LAUNCH(1, 1); break;

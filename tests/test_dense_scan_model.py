@@ -1,7 +1,7 @@
 """Host-side model of the dense agg kernel's wave algorithm.
 
 `agg_apply_dense4_body` (rw_amd.hip) splits each 64-lane x RPL-row tile
-into lane-local equal-key segments, then closes cross-lane runs with a
+(RPL = 4 rows per lane, a constant there as here) into lane-local equal-key segments, then closes cross-lane runs with a
 segmented inclusive scan over lane suffixes; exactly one commit reaches
 the table per (tile, run). The count-star call is carried as a u32 run
 length beside the scan (template param CS) instead of an i64 inside it.

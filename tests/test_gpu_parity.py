@@ -170,6 +170,39 @@ def test_agg_dense_tail_and_runs():
         run_and_compare(g, o, [[c]])
 
 
+@pytest.mark.parametrize("calls,row_count_index", [
+    ([(AGG_SUM, 1, T_I64), (AGG_MAX, 1, T_I64), (AGG_COUNT_STAR, -1, T_I64)], 2),
+    ([(AGG_COUNT_STAR, -1, T_I64), (AGG_SUM, 1, T_I64), (AGG_MIN, 1, T_I64),
+      (AGG_MAX, 1, T_I64)], 0),
+    ([(AGG_COUNT, 1, T_I64)], 0),
+    ([(AGG_COUNT, 1, T_I64), (AGG_SUM, 1, T_I64)], 0),
+], ids=["sum_max_countstar", "countstar_sum_min_max", "count", "count_sum"])
+def test_agg_dense_generic_shapes(calls, row_count_index):
+    # the generic dense kernels (rw_amd.hip agg_apply_dense4_kernel<1..4>,
+    # no count-star carried as run length): three and four calls, where
+    # count(*) rides in the scan as the constant 1, and a row count that is
+    # count(col), the only way to the <1> and <2> instantiations. 1024 rows
+    # is the dense path's minimum; 1025 and 4099 leave a partial tail tile.
+    # Sorted keys from three values give runs that cross lanes and tiles;
+    # 500 random keys give short runs, interior commits and memo misses.
+    # The second chunk and the second epoch meet existing groups.
+    rng = np.random.default_rng(11)
+    for n in (1024, 1025, 4099):
+        for sorted_keys in (True, False):
+            g, o = agg_pair(calls, row_count_index, append_only=True)
+            epochs = []
+            for _ in range(2):
+                chunks = []
+                for _ in range(2):
+                    keys = (np.sort(rng.integers(0, 3, n)) if sorted_keys
+                            else rng.integers(0, 500, n))
+                    vals = rng.integers(1, 10**7, n)
+                    chunks.append(mk_chunk([T_I64, T_I64],
+                                           np.zeros(n, np.uint8), [keys, vals]))
+                epochs.append(chunks)
+            run_and_compare(g, o, epochs)
+
+
 # ---------------- HashJoin ----------------
 
 
