@@ -40,12 +40,27 @@ enum RwTypeId {
      * u32 flags (scale in bits 16-23, sign in bit 31; byte 0 = 1/2/3 for
      * NaN/+Inf/-Inf specials) ++ u32 lo ++ u32 mid ++ u32 hi, all LE. */
     RW_T_DECIMAL = 6,
+    /* Variable-length bytes (the reference's Utf8Array / BytesArray,
+     * common/src/array/utf8_array.rs + bytes_array.rs: offsets + one byte
+     * buffer). The column's `data` points at ONE RwVarlenData. Bytes are
+     * opaque (no UTF-8 validation); the empty string is a valid value of
+     * length 0. On input the bytes of NULL rows are ignored; on output NULL
+     * rows have zero length. */
+    RW_T_VARCHAR = 7,
 };
+
+/* Payload of a RW_T_VARCHAR column: row r is bytes[offsets[r]..offsets[r+1]).
+ * `offsets` has n_rows + 1 entries, is non-decreasing, and offsets[0] == 0. */
+typedef struct RwVarlenData {
+    const uint32_t* offsets;
+    const uint8_t* bytes;
+} RwVarlenData;
 
 typedef struct RwColumn {
     uint8_t type;          /* RwTypeId */
     const uint8_t* valid;  /* n_rows bytes, 1 = non-NULL; never NULL ptr */
-    const void* data;      /* n_rows values of native width */
+    const void* data;      /* n_rows values of native width; RW_T_VARCHAR:
+                            * one RwVarlenData */
 } RwColumn;
 
 typedef struct RwChunk {
@@ -65,6 +80,8 @@ static inline uint32_t rw_type_size(uint8_t t) {
         case RW_T_BOOL: return 1;
         case RW_T_TS: return 8;
         case RW_T_DECIMAL: return 16;
+        /* RW_T_VARCHAR is not fixed width: 0. Code that sizes a column with
+         * this must reject type 7 instead of copying 0 bytes. */
         default: return 0;
     }
 }

@@ -225,6 +225,41 @@ inline size_t value_decode_datum(const uint8_t* p, size_t avail, uint8_t type,
     return 0;
 }
 
+// Varchar datums (serialize_str, value_encoding/mod.rs): presence byte, then
+// a u32 little-endian byte length, then the bytes. Separate entry points —
+// a string does not fit DatumC's 8/16-byte image.
+inline void value_encode_str(std::vector<uint8_t>& buf, bool null,
+                             const uint8_t* s, uint32_t len) {
+    if (null) {
+        buf.push_back(0);
+        return;
+    }
+    buf.push_back(1);
+    for (int k = 0; k < 4; k++) buf.push_back((uint8_t)(len >> (8 * k)));
+    buf.insert(buf.end(), s, s + len);
+}
+
+// inverse of value_encode_str: returns bytes consumed, 0 on truncation.
+// *s points INTO p (no copy); NULL yields *null = true, *len = 0.
+inline size_t value_decode_str(const uint8_t* p, size_t avail, bool* null,
+                               const uint8_t** s, uint32_t* len) {
+    if (avail < 1) return 0;
+    if (p[0] == 0) {
+        *null = true;
+        *s = p;
+        *len = 0;
+        return 1;
+    }
+    if (avail < 5) return 0;
+    uint32_t n = (uint32_t)p[1] | ((uint32_t)p[2] << 8) |
+                 ((uint32_t)p[3] << 16) | ((uint32_t)p[4] << 24);
+    if (avail - 5 < (size_t)n) return 0;
+    *null = false;
+    *s = p + 5;
+    *len = n;
+    return 5 + (size_t)n;
+}
+
 // iterate spill frames ([put u8][klen u32 LE][key][vlen u32 LE][value]);
 // calls fn(put, key_ptr, klen, val_ptr, vlen); returns false on malformed
 template <typename F>

@@ -317,6 +317,49 @@ int rw_join_checkpoint_drain(void* h, int side, uint8_t** buf, uint64_t* len);
  * loudly on pending deltas or undrained rows). Logical state, drains and
  * restore are unaffected; `reclaimed` (optional) reports freed bytes. */
 int rw_join_compact(void* h, int side, uint64_t* reclaimed);
+
+/* ----- varchar payload columns (RW_T_VARCHAR, rw_chunk.h) -----
+ * The join carries Utf8Array / BytesArray columns
+ * (common/src/array/utf8_array.rs, bytes_array.rs) as PAYLOAD on either
+ * side — Nexmark q8's P.name. rw_hash_join_create returns NULL (message
+ * names the column) when a varchar column is a join key, a pk column, a
+ * condition operand, or a watermark / inequality column; varchar keys are
+ * a later item. Each side owns one device byte arena; a cell's record word
+ * is offset (bits 0..39) | length (bits 40..63) into it. A pushed string
+ * longer than 2^24-1 bytes, or a malformed offsets array, fails the push
+ * with RW_E_INVAL before anything is copied.
+ *  - Spill values encode a varchar datum as the presence byte, a u32 LE
+ *    length and the bytes (serialize_str, value_encoding/mod.rs); keys
+ *    never hold one. rw_hash_join_restore decodes them back into the arena.
+ *  - Retractions match by string CONTENT: a delete row's bytes are resolved
+ *    against the stored row with equal fixed-width columns before the
+ *    probe. A side's live rows are unique by pk (the reference's
+ *    JoinRowSet), so at most one stored row qualifies.
+ *  - Arena bytes of retracted / watermark-cleaned rows, and the bytes a
+ *    delete row itself appended, stay allocated until rw_join_compact,
+ *    which rebuilds the arena from the live records and adds the freed
+ *    bytes to `reclaimed`.
+ *  - Not supported on an executor with varchar columns (RW_E_INVAL):
+ *    rw_hash_join_ingest_mode(h, 1), the device-batch entry points
+ *    rw_join_bench_preload/apply/run, and the device hops
+ *    rw_join_apply_aggout, rw_join_marshal_output, rw_agg_apply_joinout,
+ *    rw_join_vnode_hop, rw_q7pipe_bench_run.
+ *
+ * rw_hash_join_varlen_reserve sets `side`'s initial arena capacity in
+ * bytes; legal only before any input or restore (RW_E_INVAL otherwise, and
+ * for a side without varchar columns). Without it the arena starts at
+ * 1 MiB; either way it doubles on demand. rw_hash_join_varlen_stats
+ * reports the arena's used and allocated bytes (0/0 for a side without
+ * varchar columns). */
+int rw_hash_join_varlen_reserve(void* h, int side, uint64_t bytes);
+int rw_hash_join_varlen_stats(void* h, int side, uint64_t* used,
+                              uint64_t* capacity);
+/* Cumulative figures of the emit path's string materialisation since
+ * create (tests/bench_varchar_emit.py): `ms` = device time of length +
+ * scan + copy per varchar output column, `copy_ms` = the copy kernel's
+ * share, `bytes` = packed output bytes, `launches` = materialisations. */
+int rw_hash_join_varlen_emit_stats(void* h, double* ms, double* copy_ms,
+                                   uint64_t* bytes, uint64_t* launches);
 /* Same reclamation for the agg's materialized-input row store and the
  * GroupTopN record store (retractions retire rows in place). Same
  * contract: call after the drains; fails loudly on pending deltas. */

@@ -30,8 +30,11 @@
 #include <unordered_set>
 #include <vector>
 
+#include <rocprim/device/device_scan.hpp>
+
 #include "../../include/rw_codec.hpp"
 #include "../../include/rw_stream.h"
+#include "../../include/rw_varlen.hpp"
 
 #define WAVE 64
 
@@ -381,6 +384,10 @@ struct JoinSideDev {
     uint32_t* deg_dirty_flag;
     uint32_t* deg_dirty_list;
     uint32_t* deg_dirty_n;
+    // byte arena of the side's RW_T_VARCHAR cells (rw_varlen.hpp words
+    // index it; null for sides without varchar columns). Last field: the
+    // probe kernels never read it.
+    uint8_t* arena;
 };
 
 __device__ __forceinline__ JoinRowHdr* jrow(const JoinSideDev& s, uint32_t r) {
@@ -3721,7 +3728,16 @@ void rw_chunk_free(RwChunk* ch) {
     if (!ch) return;
     for (uint32_t c = 0; c < ch->n_cols; c++) {
         delete[] ch->cols[c].valid;
-        delete[] (int64_t*)ch->cols[c].data;
+        if (ch->cols[c].type == RW_T_VARCHAR) {
+            auto* vd = (const RwVarlenData*)ch->cols[c].data;
+            if (vd) {
+                delete[] vd->offsets;
+                delete[] vd->bytes;
+                delete vd;
+            }
+        } else {
+            delete[] (int64_t*)ch->cols[c].data;
+        }
     }
     delete[] ch->cols;
     delete[] ch->ops;
@@ -4277,6 +4293,9 @@ int rw_vnode_compute(const RwVnodeDesc* d, const RwChunk* chunk, uint16_t* out) 
         const RwColumn& c = chunk->cols[d->key_indices[k]];
         types[k] = c.type;
         if (c.type == RW_T_BOOL) FAIL(RW_E_INVAL, "bool vnode key unsupported on GPU");
+        if (c.type == RW_T_VARCHAR)
+            FAIL(RW_E_INVAL, "varchar vnode key (column %u) unsupported",
+                 d->key_indices[k]);
         HIP_TRY(hipMalloc(&b.col_vals[k], (size_t)n * 8));
         HIP_TRY(hipMalloc(&b.col_valid[k], n));
         if (c.type == RW_T_I32 || c.type == RW_T_F32) {
@@ -4322,6 +4341,11 @@ typedef struct {
 int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
                         RwChunk** outs) {
     uint32_t n = chunk->n_rows;
+    // the per-output column copies below size by rw_type_size, which is 0
+    // for the variable-width type: dispatch of varchar columns is not built
+    for (uint32_t c = 0; c < chunk->n_cols; c++)
+        if (chunk->cols[c].type == RW_T_VARCHAR)
+            FAIL(RW_E_INVAL, "dispatch of varchar column %u unsupported", c);
     std::vector<uint16_t> vnodes(n);
     int rc = rw_vnode_compute(&d->v, chunk, vnodes.data());
     if (rc != RW_OK) return rc;
@@ -4423,6 +4447,7 @@ struct JoinMeta {
     uint8_t append_only;
     uint8_t join_type;    // RwJoinType
     uint8_t need_deg[2];  // need_left/right_degree (join/mod.rs:153-165)
+    uint8_t vc_mask[2];   // bit c = column c of the side is RW_T_VARCHAR
 };
 
 struct JoinBatchDev {
@@ -6326,6 +6351,241 @@ __global__ void join_vnode_scope_kernel(JoinSideDev sd, int KW,
     }
 }
 
+// ============ varchar payload columns ============
+//
+// A varchar cell is an 8-byte reference word (rw_varlen.hpp) into its
+// side's byte arena, so the probe kernels above move it like an i64. The
+// kernels here are everything that has to look THROUGH a word: resolving
+// retractions by string content, materialising strings for emit / drain,
+// and rebuilding the arena at compaction.
+
+// n reference words, word i at words[i * stride] (stride in 8-byte units:
+// 1 for a columnar block, row_stride / 8 for a column of packed records).
+// Optional masks yield the zero word (length 0): nulls[i] != 0 (the join
+// output block's NULL flags) and ops[i] == 0xFF for i < sparse_n (the inner
+// probe's pre-assigned sparse region — those slots hold unwritten words).
+struct VarlenView {
+    const uint64_t* words;
+    uint32_t stride;
+    const uint8_t* nulls;
+    const uint8_t* ops;
+    uint32_t sparse_n;
+};
+
+__device__ __forceinline__ uint64_t varlen_view_word(const VarlenView& v,
+                                                     uint32_t i) {
+    if (v.ops && i < v.sparse_n && v.ops[i] == 0xFF) return 0;
+    if (v.nulls && v.nulls[i]) return 0;
+    return v.words[(size_t)i * v.stride];
+}
+
+// lens[i] = byte length of cell i for i < n; lens[n] = 0 so an exclusive
+// scan over n + 1 entries leaves the total at offs[n]
+__global__ void varlen_len_kernel(VarlenView v, uint32_t n, uint64_t* lens) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n;
+         i += stride)
+        lens[i] = i < n ? rwvarlen::word_len(varlen_view_word(v, i)) : 0;
+}
+
+// OUTPUT-CENTRIC copy: each lane owns one aligned W-byte unit (a dword or
+// 16 bytes) of the packed buffer, finds the string holding its first byte
+// by binary search over the scanned offsets (the search's top levels hit
+// the same few lines for every lane of a wave), gathers its <= W source
+// bytes (they may span several short strings) and stores the unit
+// coalesced. `out` holds (total + W - 1) / W whole units.
+template <int W>
+__global__ __launch_bounds__(256) void varlen_copy_out_kernel(
+    VarlenView v, const uint8_t* __restrict__ arena,
+    const uint64_t* __restrict__ offs, uint32_t n, uint64_t total,
+    uint8_t* __restrict__ out) {
+    static_assert(W == 4 || W == 16, "unit is a dword or four");
+    uint64_t units = (total + W - 1) / W;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         t < units; t += stride) {
+        uint64_t p = t * W;
+        // largest i with offs[i] <= p; offs[0] = 0 <= p < total = offs[n],
+        // so offs[i + 1] > p: string i is non-empty and holds byte p
+        uint32_t lo = 0, hi = n;
+        while (hi - lo > 1) {
+            uint32_t mid = lo + (hi - lo) / 2;
+            if (offs[mid] <= p) lo = mid;
+            else hi = mid;
+        }
+        uint32_t i = lo;
+        uint64_t beg = offs[i], end = offs[i + 1];
+        const uint8_t* src = arena + rwvarlen::word_off(varlen_view_word(v, i));
+        uint32_t dw[W / 4] = {};
+#pragma unroll
+        for (int k = 0; k < W; k++) {
+            uint64_t q = p + k;
+            if (q < total) {
+                while (q >= end) { // q < offs[n]: i + 1 <= n stays in range
+                    i++;
+                    beg = end;
+                    end = offs[i + 1];
+                    src = arena +
+                          rwvarlen::word_off(varlen_view_word(v, i));
+                }
+                dw[k >> 2] |= (uint32_t)src[q - beg] << (8 * (k & 3));
+            }
+        }
+        if (W == 4)
+            ((uint32_t*)out)[t] = dw[0];
+        else
+            ((uint4*)out)[t] = make_uint4(dw[0], dw[W / 4 > 1 ? 1 : 0],
+                                          dw[W / 4 > 2 ? 2 : 0],
+                                          dw[W / 4 > 3 ? 3 : 0]);
+    }
+}
+
+// the obvious form, and the one in use: one string per lane, byte loop.
+// Neighbouring lanes write neighbouring short strings, so the stores of a
+// wave still land in a few adjacent lines.
+__global__ __launch_bounds__(256) void varlen_copy_lane_kernel(
+    VarlenView v, const uint8_t* __restrict__ arena,
+    const uint64_t* __restrict__ offs, uint32_t n,
+    uint8_t* __restrict__ out) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        uint64_t w = varlen_view_word(v, i);
+        uint32_t len = rwvarlen::word_len(w);
+        const uint8_t* src = arena + rwvarlen::word_off(w);
+        uint8_t* dst = out + offs[i];
+        for (uint32_t k = 0; k < len; k++) dst[k] = src[k];
+    }
+}
+
+// bytes the copy may store past `total`: out buffers are padded to this
+#define VARLEN_COPY_PAD 16
+
+static void varlen_copy_launch(const VarlenView& v, const uint8_t* arena,
+                               const uint64_t* offs, uint32_t n,
+                               uint64_t total, uint8_t* out,
+                               hipStream_t stream) {
+    // Default = the measured winner on the q8 emit shape:
+    // the per-string lane loop, 72 us per 1M names of 8-32 bytes, against
+    // 135 us (dword units) and 240 us (16-byte units) for the
+    // output-centric form, whose serial per-lane walk across string
+    // boundaries costs more than its coalesced stores save.
+    // RW_VARLEN_COPY=dword|b16 selects those for the A/B in
+    // tests/bench_varchar_emit.py.
+    const char* e = getenv("RW_VARLEN_COPY");
+    const bool out_centric = e && (!strcmp(e, "dword") || !strcmp(e, "b16"));
+    if (!out_centric) {
+        uint32_t blocks = (n + 255) / 256;
+        if (blocks > 16384) blocks = 16384;
+        varlen_copy_lane_kernel<<<blocks, 256, 0, stream>>>(v, arena, offs, n,
+                                                            out);
+        return;
+    }
+    const int W = !strcmp(e, "dword") ? 4 : 16;
+    uint64_t units = (total + W - 1) / W;
+    uint64_t blocks = (units + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (W == 4)
+        varlen_copy_out_kernel<4><<<(uint32_t)blocks, 256, 0, stream>>>(
+            v, arena, offs, n, total, out);
+    else
+        varlen_copy_out_kernel<16><<<(uint32_t)blocks, 256, 0, stream>>>(
+            v, arena, offs, n, total, out);
+}
+
+// Retraction pre-pass (cold path; runs before a probe launch whose range
+// holds delete rows, only for sides with varchar columns). jown_delete
+// matches a delete row against the stored record by 8-byte word compare,
+// but the delete row's string was appended at a different arena offset
+// than the stored one. For each delete row this kernel walks the own-side
+// bucket chain for the live record that equals the row on every
+// fixed-width column (a superset of join key ∥ pk) and, by arena BYTES, on
+// every varchar column; on a hit it rewrites the batch row's varchar
+// word(s) to the stored record's, after which the probe kernel's compare
+// works unchanged. ASSUMPTION: a side's live rows are unique by pk (the
+// reference's JoinRowSet is keyed by pk), so at most one record qualifies;
+// with duplicate live rows two same-launch deletes could resolve to the
+// same record. No hit leaves the words alone: the delete then finds
+// nothing, exactly like a non-matching i64 delete. The own side is not
+// mutated during this launch, so plain loads suffice.
+__global__ void join_varlen_resolve_kernel(JoinBatchDev b, JoinSideDev own,
+                                           JoinMeta m, int S, uint32_t r0,
+                                           uint32_t r1) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t vcm = m.vc_mask[S];
+    for (uint32_t r = r0 + blockIdx.x * blockDim.x + threadIdx.x; r < r1;
+         r += stride) {
+        if (b.vis && !b.vis[r]) continue;
+        uint8_t op = b.ops[r];
+        if (op == RW_OP_INSERT || op == RW_OP_UPDATE_INSERT) continue;
+        int64_t kw[MAX_KW];
+        uint32_t nullmask = 0;
+        for (int i = 0; i < m.KW; i++) {
+            uint8_t col = m.key_cols[S][i];
+            bool valid = b.col_valid[col][r];
+            kw[i] = valid ? b.col_vals[col][r] : 0;
+            nullmask |= (!valid) << i;
+        }
+        if (nullmask & ~(uint32_t)m.null_safe_mask) continue; // never stored
+        uint32_t row = jbucket_head(own, hash_key(kw, nullmask, m.KW), false);
+        while (row != UINT32_MAX) {
+            JoinRowHdr* h = jrow(own, row);
+            if (h->alive) {
+                uint32_t vb = h->validbits;
+                const long long* hv = jvals(h);
+                bool eq = true;
+                for (int c = 0; eq && c < m.n_cols[S]; c++) {
+                    bool va = b.col_valid[c][r] != 0;
+                    if (va != (bool)((vb >> c) & 1)) {
+                        eq = false;
+                    } else if (va && !((vcm >> c) & 1)) {
+                        eq = b.col_vals[c][r] == hv[c];
+                    } else if (va) {
+                        uint64_t wa = (uint64_t)b.col_vals[c][r];
+                        uint64_t wr = (uint64_t)hv[c];
+                        uint32_t len = rwvarlen::word_len(wa);
+                        if (len != rwvarlen::word_len(wr)) {
+                            eq = false;
+                        } else if (wa != wr) {
+                            const uint8_t* pa =
+                                own.arena + rwvarlen::word_off(wa);
+                            const uint8_t* pr =
+                                own.arena + rwvarlen::word_off(wr);
+                            for (uint32_t k = 0; eq && k < len; k++)
+                                eq = pa[k] == pr[k];
+                        }
+                    }
+                }
+                if (eq) {
+                    for (int c = 0; c < m.n_cols[S]; c++)
+                        if (((vcm >> c) & 1) && ((vb >> c) & 1))
+                            b.col_vals[c][r] = hv[c];
+                    break;
+                }
+            }
+            row = h->next;
+        }
+    }
+}
+
+// compaction: point every live record's varchar word at its string's new
+// home (new_base + offs[i]); NULL cells keep word 0
+__global__ void varlen_rewrite_kernel(JoinSideDev sd, int col, uint32_t n,
+                                      const uint64_t* offs,
+                                      uint64_t new_base) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += stride) {
+        JoinRowHdr* h = jrow(sd, i);
+        long long* hv = jvals(h);
+        bool valid = (h->validbits >> col) & 1;
+        hv[col] = valid ? (long long)rwvarlen::pack(
+                              new_base + offs[i],
+                              rwvarlen::word_len((uint64_t)hv[col]))
+                        : 0;
+    }
+}
+
 struct HashJoin {
     RwHashJoinDesc desc;
     JoinMeta m{};
@@ -6396,9 +6656,59 @@ struct HashJoin {
         types[0].assign(d->types_l, d->types_l + d->n_cols_l);
         types[1].assign(d->types_r, d->types_r + d->n_cols_r);
         for (int s = 0; s < 2; s++)
-            for (auto t : types[s])
-                if (t != RW_T_I64 && t != RW_T_TS)
-                    FAIL(RW_E_INVAL, "column type %d unsupported on GPU (i64/ts only)", t);
+            for (size_t c = 0; c < types[s].size(); c++) {
+                uint8_t t = types[s][c];
+                if (t == RW_T_VARCHAR)
+                    m.vc_mask[s] |= (uint8_t)(1u << c);
+                else if (t != RW_T_I64 && t != RW_T_TS)
+                    FAIL(RW_E_INVAL, "column type %d unsupported on GPU "
+                                     "(i64/ts, varchar payload only)", t);
+            }
+        // varchar is a PAYLOAD type: every column the kernels compare or
+        // hash as an 8-byte scalar must be fixed width (rw_stream.h)
+        {
+            const char* sn[2] = {"left", "right"};
+            auto is_vc = [&](int s, uint32_t col) {
+                return col < types[s].size() && types[s][col] == RW_T_VARCHAR;
+            };
+            auto is_vc_cat = [&](uint32_t idx) {
+                return idx < d->n_cols_l ? is_vc(0, idx)
+                                         : is_vc(1, idx - d->n_cols_l);
+            };
+            for (uint32_t i = 0; i < d->n_key; i++) {
+                if (is_vc(0, d->key_l[i]))
+                    FAIL(RW_E_INVAL, "varchar %s column %u cannot be a join key",
+                         sn[0], d->key_l[i]);
+                if (is_vc(1, d->key_r[i]))
+                    FAIL(RW_E_INVAL, "varchar %s column %u cannot be a join key",
+                         sn[1], d->key_r[i]);
+            }
+            for (uint32_t i = 0; i < d->n_pk_l; i++)
+                if (is_vc(0, d->pk_l[i]))
+                    FAIL(RW_E_INVAL, "varchar %s column %u cannot be a pk column",
+                         sn[0], d->pk_l[i]);
+            for (uint32_t i = 0; i < d->n_pk_r; i++)
+                if (is_vc(1, d->pk_r[i]))
+                    FAIL(RW_E_INVAL, "varchar %s column %u cannot be a pk column",
+                         sn[1], d->pk_r[i]);
+            if (d->has_cond && (is_vc_cat(d->cond_l) || is_vc_cat(d->cond_r)))
+                FAIL(RW_E_INVAL, "varchar column %u cannot be a condition operand",
+                     is_vc_cat(d->cond_l) ? d->cond_l : d->cond_r);
+            if (d->has_cond && d->has_cond2 &&
+                (is_vc_cat(d->cond2_l) || is_vc_cat(d->cond2_r)))
+                FAIL(RW_E_INVAL, "varchar column %u cannot be a condition operand",
+                     is_vc_cat(d->cond2_l) ? d->cond2_l : d->cond2_r);
+            for (uint32_t p = 0; p < d->n_ineq; p++) {
+                if (is_vc(0, d->ineq_left_col[p]))
+                    FAIL(RW_E_INVAL, "varchar %s column %u cannot be an "
+                                     "inequality/watermark column",
+                         sn[0], d->ineq_left_col[p]);
+                if (is_vc(1, d->ineq_right_col[p]))
+                    FAIL(RW_E_INVAL, "varchar %s column %u cannot be an "
+                                     "inequality/watermark column",
+                         sn[1], d->ineq_right_col[p]);
+            }
+        }
         for (uint32_t i = 0; i < d->n_key; i++) {
             m.key_cols[0][i] = (uint8_t)d->key_l[i];
             m.key_cols[1][i] = (uint8_t)d->key_r[i];
@@ -6536,12 +6846,188 @@ struct HashJoin {
         return RW_OK;
     }
 
+    // ----- varchar payload columns: per-side byte arena -----
+    static constexpr uint64_t ARENA_DEFAULT = 1ull << 20;
+    uint64_t arena_used[2] = {0, 0};
+    uint64_t arena_cap[2] = {0, 0};     // allocated bytes
+    uint64_t arena_reserve[2] = {0, 0}; // requested initial capacity
+    bool seen_input = false;            // any push or restore happened
+    // host staging of a batch's reference words; lives until the next
+    // upload so the async H2D copy never outlives its source
+    std::vector<int64_t> vwords[2][MAX_COLS];
+    // emit-path materialisation scratch + stats
+    uint64_t* d_vlens = nullptr;
+    uint64_t* d_voffs = nullptr;
+    uint32_t d_vcap = 0;
+    uint8_t* d_vbytes = nullptr;
+    uint64_t d_vbytes_cap = 0;
+    void* d_scan_tmp = nullptr;
+    size_t d_scan_tmp_cap = 0;
+    hipEvent_t vev0 = nullptr, vev1 = nullptr, vev2 = nullptr;
+    double vemit_ms = 0, vcopy_ms = 0; // whole materialise / copy kernel
+    uint64_t vemit_bytes = 0, vemit_launches = 0;
+
+    bool has_varchar() const { return (m.vc_mask[0] | m.vc_mask[1]) != 0; }
+
+    // make room for `extra` more bytes: reallocate + D2D copy between
+    // launches (words are offsets, so none is rewritten)
+    int arena_ensure(int s, uint64_t extra) {
+        uint64_t need = arena_used[s] + extra;
+        if (need > rwvarlen::MAX_OFF)
+            FAIL(RW_E_INVAL, "varchar arena would exceed 2^40-1 bytes");
+        if (side[s].arena && need <= arena_cap[s]) return RW_OK;
+        uint64_t cap = arena_cap[s] ? arena_cap[s]
+                       : arena_reserve[s] ? arena_reserve[s] : ARENA_DEFAULT;
+        while (cap < need) cap *= 2;
+        uint8_t* na = nullptr;
+        HIP_TRY(hipMalloc(&na, cap));
+        if (side[s].arena) {
+            // in-flight launches may still read the old buffer
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (arena_used[s])
+                HIP_TRY(hipMemcpy(na, side[s].arena, arena_used[s],
+                                  hipMemcpyDeviceToDevice));
+            hipFree(side[s].arena);
+        }
+        side[s].arena = na;
+        arena_cap[s] = cap;
+        return RW_OK;
+    }
+
+    int ensure_vscratch(uint32_t n) {
+        if (d_vcap >= n + 1) return RW_OK;
+        if (d_vlens) hipFree(d_vlens);
+        if (d_voffs) hipFree(d_voffs);
+        d_vlens = d_voffs = nullptr;
+        d_vcap = 0;
+        uint32_t cap = 4096;
+        while (cap < n + 1) cap <<= 1;
+        HIP_TRY(hipMalloc(&d_vlens, (size_t)cap * 8));
+        HIP_TRY(hipMalloc(&d_voffs, (size_t)cap * 8));
+        d_vcap = cap;
+        return RW_OK;
+    }
+
+    // Materialise the strings a view's words reference into ONE packed
+    // host byte buffer: length kernel -> exclusive scan -> copy kernel ->
+    // D2H. offs gets n + 1 entries (offs[n] = total bytes).
+    int varlen_fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
+                     std::vector<uint64_t>& offs, std::vector<uint8_t>& bytes,
+                     bool timed) {
+        offs.assign((size_t)n + 1, 0);
+        bytes.clear();
+        if (!n) return RW_OK;
+        int rc = ensure_vscratch(n);
+        if (rc != RW_OK) return rc;
+        if (timed && !vev0) {
+            HIP_TRY(hipEventCreate(&vev0));
+            HIP_TRY(hipEventCreate(&vev1));
+            HIP_TRY(hipEventCreate(&vev2));
+        }
+        if (timed) HIP_TRY(hipEventRecord(vev0, stream));
+        uint32_t blocks = (n + 1 + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        varlen_len_kernel<<<blocks, 256, 0, stream>>>(v, n, d_vlens);
+        size_t tmp = 0;
+        HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, d_vlens, d_voffs,
+                                        (uint64_t)0, (size_t)n + 1,
+                                        rocprim::plus<uint64_t>(), stream));
+        if (tmp > d_scan_tmp_cap) {
+            if (d_scan_tmp) hipFree(d_scan_tmp);
+            d_scan_tmp = nullptr;
+            d_scan_tmp_cap = 0;
+            HIP_TRY(hipMalloc(&d_scan_tmp, tmp));
+            d_scan_tmp_cap = tmp;
+        }
+        HIP_TRY(rocprim::exclusive_scan(d_scan_tmp, tmp, d_vlens, d_voffs,
+                                        (uint64_t)0, (size_t)n + 1,
+                                        rocprim::plus<uint64_t>(), stream));
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, d_voffs + n, 8, hipMemcpyDeviceToHost,
+                               stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (total) {
+            uint64_t padded = total + VARLEN_COPY_PAD; // whole copy units
+            if (d_vbytes_cap < padded) {
+                if (d_vbytes) hipFree(d_vbytes);
+                d_vbytes = nullptr;
+                d_vbytes_cap = 0;
+                uint64_t cap = 1ull << 16;
+                while (cap < padded) cap <<= 1;
+                HIP_TRY(hipMalloc(&d_vbytes, cap));
+                d_vbytes_cap = cap;
+            }
+            if (timed) HIP_TRY(hipEventRecord(vev2, stream));
+            varlen_copy_launch(v, arena, d_voffs, n, total, d_vbytes, stream);
+        }
+        if (timed) {
+            HIP_TRY(hipEventRecord(vev1, stream));
+            HIP_TRY(hipEventSynchronize(vev1));
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, vev0, vev1));
+            vemit_ms += ms;
+            if (total) {
+                HIP_TRY(hipEventElapsedTime(&ms, vev2, vev1));
+                vcopy_ms += ms;
+            }
+            vemit_bytes += total;
+            vemit_launches++;
+        }
+        HIP_TRY(hipMemcpy(offs.data(), d_voffs, ((size_t)n + 1) * 8,
+                          hipMemcpyDeviceToHost));
+        bytes.resize(total);
+        if (total)
+            HIP_TRY(hipMemcpy(bytes.data(), d_vbytes, total,
+                              hipMemcpyDeviceToHost));
+        return RW_OK;
+    }
+
     int upload(int s, const RwChunk* c, JoinBatchDev* bout) {
         uint32_t n = c->n_rows;
+        // varchar columns: validate every offsets array BEFORE any copy
+        for (int ci = 0; m.vc_mask[s] && ci < m.n_cols[s]; ci++) {
+            if (!((m.vc_mask[s] >> ci) & 1)) continue;
+            if (c->cols[ci].type != RW_T_VARCHAR)
+                FAIL(RW_E_INVAL, "column %d: expected a varchar column", ci);
+            auto* vd = (const RwVarlenData*)c->cols[ci].data;
+            const char* why =
+                vd ? rwvarlen::validate_offsets(vd->offsets, n) : "data is NULL";
+            if (why) FAIL(RW_E_INVAL, "varchar column %d: %s", ci, why);
+            if (n && vd->offsets[n] && !vd->bytes)
+                FAIL(RW_E_INVAL, "varchar column %d: bytes is NULL", ci);
+        }
+        seen_input = true;
         int rc = ensure_stage(s, n);
         if (rc != RW_OK) return rc;
         JoinBatchDev b = stage[s];
         for (int ci = 0; ci < m.n_cols[s]; ci++) {
+            if ((m.vc_mask[s] >> ci) & 1) {
+                // append the chunk's bytes at the arena tail (one H2D copy)
+                // and stage reference words where i64 values go
+                auto* vd = (const RwVarlenData*)c->cols[ci].data;
+                uint64_t total = n ? vd->offsets[n] : 0;
+                rc = arena_ensure(s, total);
+                if (rc != RW_OK) return rc;
+                uint64_t base = arena_used[s];
+                if (total)
+                    HIP_TRY(hipMemcpyAsync(side[s].arena + base, vd->bytes,
+                                           total, hipMemcpyHostToDevice,
+                                           stream));
+                arena_used[s] += total;
+                auto& w = vwords[s][ci];
+                w.resize(n);
+                for (uint32_t r = 0; r < n; r++)
+                    w[r] = c->cols[ci].valid[r]
+                               ? (int64_t)rwvarlen::pack(
+                                     base + vd->offsets[r],
+                                     vd->offsets[r + 1] - vd->offsets[r])
+                               : 0;
+                HIP_TRY(hipMemcpyAsync(b.col_vals[ci], w.data(), (size_t)n * 8,
+                                       hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(b.col_valid[ci], c->cols[ci].valid, n,
+                                       hipMemcpyHostToDevice, stream));
+                continue;
+            }
             HIP_TRY(hipMemcpyAsync(b.col_vals[ci], c->cols[ci].data, (size_t)n * 8,
                                    hipMemcpyHostToDevice, stream));
             HIP_TRY(hipMemcpyAsync(b.col_valid[ci], c->cols[ci].valid, n,
@@ -6738,10 +7224,55 @@ struct HashJoin {
             for (int i = 0; i < m.n_pk[s]; i++) put_datum(m.pk_cols[s][i]);
             k.assign((const char*)kb.data(), kb.size());
         };
+        // varchar cells of the fresh records: fetch their strings with the
+        // emit path's gather kernels (one strided view per column over the
+        // uploaded copy of the fresh range; dead records and NULL cells
+        // are masked to length 0 host-side before the upload)
+        std::vector<std::vector<uint64_t>> voffs(m.n_cols[s]);
+        std::vector<std::vector<uint8_t>> vbytes(m.n_cols[s]);
+        if (m.vc_mask[s] && cur > mark) {
+            uint32_t nf = cur - mark;
+            std::vector<uint64_t> words(nf);
+            uint64_t* d_words = nullptr;
+            HIP_TRY(hipMalloc(&d_words, (size_t)nf * 8));
+            for (int c = 0; c < m.n_cols[s]; c++) {
+                if (!((m.vc_mask[s] >> c) & 1)) continue;
+                for (uint32_t i = 0; i < nf; i++) {
+                    const uint8_t* rec = fresh.data() + (size_t)i * stride;
+                    const uint32_t* hd = (const uint32_t*)rec;
+                    bool live = hd[0] && ((hd[2] >> c) & 1);
+                    words[i] = live ? ((const uint64_t*)(rec + 16))[c] : 0;
+                }
+                if (hipMemcpy(d_words, words.data(), (size_t)nf * 8,
+                              hipMemcpyHostToDevice) != hipSuccess) {
+                    hipFree(d_words);
+                    FAIL(RW_E_INTERNAL, "drain string gather failed");
+                }
+                VarlenView v{};
+                v.words = d_words;
+                v.stride = 1;
+                int rcv = varlen_fetch(v, js.arena, nf, voffs[c], vbytes[c],
+                                       false);
+                if (rcv != RW_OK) {
+                    hipFree(d_words);
+                    return rcv;
+                }
+            }
+            hipFree(d_words);
+        }
         auto encode_val = [&](const uint8_t* rec, std::vector<uint8_t>& v) {
             const uint32_t vb = ((const uint32_t*)rec)[2];
             const int64_t* vals = (const int64_t*)(rec + 16);
             for (int c = 0; c < m.n_cols[s]; c++) {
+                if ((m.vc_mask[s] >> c) & 1) {
+                    // only fresh records are value-encoded (PUT frames)
+                    size_t i = (size_t)(rec - fresh.data()) / stride;
+                    uint64_t o0 = voffs[c][i], o1 = voffs[c][i + 1];
+                    rwcodec::value_encode_str(v, !((vb >> c) & 1),
+                                              vbytes[c].data() + o0,
+                                              (uint32_t)(o1 - o0));
+                    continue;
+                }
                 rwcodec::DatumC d{!((vb >> c) & 1), vals[c], 0};
                 rwcodec::value_encode_datum(v, types[s][c], d);
             }
@@ -6897,6 +7428,25 @@ struct HashJoin {
                                   hipMemcpyDeviceToHost));
             }
             HIP_TRY(hipMemcpy(ops.data(), out.ops, n_out, hipMemcpyDeviceToHost));
+            // varchar output columns: the words above reference the arena
+            // of the side the column comes from — materialise the strings
+            // on the device (over the UNCOMPACTED block: NULL cells and
+            // sparse-region sentinel rows yield length 0)
+            std::vector<std::vector<uint64_t>> voffs(m.n_out);
+            std::vector<std::vector<uint8_t>> vbytes(m.n_out);
+            for (int ci = 0; ci < m.n_out; ci++) {
+                if (out_types[ci] != RW_T_VARCHAR) continue;
+                VarlenView v{};
+                v.words = (const uint64_t*)(out.vals + (size_t)ci * out.cap);
+                v.stride = 1;
+                v.nulls = out.nulls + (size_t)ci * out.cap;
+                v.ops = sparse_out ? out.ops : nullptr;
+                v.sparse_n = sparse_out ? last_sparse_rows : 0;
+                int rcv = varlen_fetch(v, side[m.out_src[ci]].arena, n_out,
+                                       voffs[ci], vbytes[ci], true);
+                if (rcv != RW_OK) return rcv;
+            }
+            std::vector<uint32_t> src_idx; // compacted row -> block row
             if (sparse_out) {
                 // compact the pre-assigned sparse region (sentinel 0xFF)
                 std::vector<uint32_t> real;
@@ -6922,6 +7472,7 @@ struct HashJoin {
                 ops.swap(co);
                 n_out = nc;
                 sparse_out = false;
+                src_idx.swap(real);
             }
             if (!n_out) {
                 HIP_TRY(hipMemset(out.counters, 0, 8));
@@ -6937,6 +7488,40 @@ struct HashJoin {
                 auto* o = new uint8_t[take];
                 memcpy(o, ops.data() + start, take);
                 for (int ci = 0; ci < m.n_out; ci++) {
+                    if (out_types[ci] == RW_T_VARCHAR) {
+                        // slice the packed buffer: this chunk's own bytes
+                        // with offsets rebased to 0
+                        const auto& vo = voffs[ci];
+                        auto blk = [&](uint32_t r) {
+                            return src_idx.empty() ? start + r
+                                                   : src_idx[start + r];
+                        };
+                        uint64_t tot = 0;
+                        for (uint32_t r = 0; r < take; r++)
+                            tot += vo[blk(r) + 1] - vo[blk(r)];
+                        if (tot > UINT32_MAX)
+                            FAIL(RW_E_INTERNAL,
+                                 "output chunk strings exceed 4 GiB; lower "
+                                 "chunk_size");
+                        auto* offs = new uint32_t[take + 1];
+                        auto* bytes = new uint8_t[tot ? tot : 1];
+                        auto* valid = new uint8_t[take];
+                        uint32_t at = 0;
+                        for (uint32_t r = 0; r < take; r++) {
+                            uint64_t o0 = vo[blk(r)], o1 = vo[blk(r) + 1];
+                            offs[r] = at;
+                            if (o1 > o0)
+                                memcpy(bytes + at, vbytes[ci].data() + o0,
+                                       o1 - o0);
+                            at += (uint32_t)(o1 - o0);
+                            valid[r] = !nulls[(size_t)ci * n_out + start + r];
+                        }
+                        offs[take] = at;
+                        cols[ci].type = RW_T_VARCHAR;
+                        cols[ci].valid = valid;
+                        cols[ci].data = new RwVarlenData{offs, bytes};
+                        continue;
+                    }
                     auto* data = new int64_t[take];
                     auto* valid = new uint8_t[take];
                     for (uint32_t r = 0; r < take; r++) {
@@ -6981,6 +7566,16 @@ struct HashJoin {
             for (int ci = 0; ci < m.n_cols[s]; ci++) {
                 uint8_t valid = c->cols[ci].valid[r];
                 k.push_back((char)valid);
+                if ((m.vc_mask[s] >> ci) & 1) {
+                    // row identity is the string's BYTES (length-prefixed
+                    // so adjacent cells cannot alias)
+                    auto* vd = (const RwVarlenData*)c->cols[ci].data;
+                    uint32_t o0 = vd->offsets[r];
+                    uint32_t len = valid ? vd->offsets[r + 1] - o0 : 0;
+                    k.append((const char*)&len, 4);
+                    if (len) k.append((const char*)vd->bytes + o0, len);
+                    continue;
+                }
                 int64_t v = valid ? ((const int64_t*)c->cols[ci].data)[r] : 0;
                 k.append((const char*)&v, 8);
             }
@@ -7099,16 +7694,37 @@ struct HashJoin {
         int rc = upload(s, c, &b);
         if (rc != RW_OK) return rc;
         std::vector<uint32_t> bounds = conflict_segments(s, c);
+        // varchar sides: delete rows resolve their strings against the
+        // stored records before each segment's probe (see the kernel)
+        std::vector<uint32_t> del_before; // deletes in rows [0, r)
+        if (m.vc_mask[s] && !b.all_insert) {
+            del_before.assign((size_t)b.n_rows + 1, 0);
+            for (uint32_t r = 0; r < b.n_rows; r++) {
+                bool vis = !(c->vis && !c->vis[r]);
+                bool del = c->ops[r] == RW_OP_DELETE ||
+                           c->ops[r] == RW_OP_UPDATE_DELETE;
+                del_before[r + 1] = del_before[r] + (vis && del);
+            }
+        }
+        auto run_segment = [&](uint32_t r0, uint32_t r1) -> int {
+            if (!del_before.empty() && del_before[r1] != del_before[r0]) {
+                uint32_t blocks = (r1 - r0 + 255) / 256;
+                if (blocks > 2048) blocks = 2048;
+                join_varlen_resolve_kernel<<<blocks, 256, 0, stream>>>(
+                    b, side[s], m, s, r0, r1);
+            }
+            return probe(s, b, true, r0, r1);
+        };
         uint32_t start = 0;
         for (uint32_t bnd : bounds) {
             if (bnd > start) {
-                rc = probe(s, b, true, start, bnd);
+                rc = run_segment(start, bnd);
                 if (rc != RW_OK) return rc;
             }
             start = bnd;
         }
         if (start < b.n_rows) {
-            rc = probe(s, b, true, start, b.n_rows);
+            rc = run_segment(start, b.n_rows);
             if (rc != RW_OK) return rc;
         }
         HIP_TRY(hipStreamSynchronize(stream));
@@ -7222,8 +7838,19 @@ struct HashJoin {
             hipFree(d_emit_count);
         }
         if (d_vis_scratch) hipFree(d_vis_scratch);
-        for (int s = 0; s < 2; s++)
+        if (d_vlens) hipFree(d_vlens);
+        if (d_voffs) hipFree(d_voffs);
+        if (d_vbytes) hipFree(d_vbytes);
+        if (d_scan_tmp) hipFree(d_scan_tmp);
+        if (vev0) {
+            hipEventDestroy(vev0);
+            hipEventDestroy(vev1);
+            if (vev2) hipEventDestroy(vev2);
+        }
+        for (int s = 0; s < 2; s++) {
             if (compact_scratch[s]) hipFree(compact_scratch[s]);
+            if (side[s].arena) hipFree(side[s].arena);
+        }
         for (int s = 0; s < 2; s++) {
             JoinSideDev& js = side[s];
             if (js.slots8) {
@@ -7275,7 +7902,56 @@ int rw_hash_join_ingest_mode(void* h, int epoch_batched) {
     auto* j = (HashJoin*)h;
     if (!epoch_batched && j->pend_side >= 0)
         FAIL(RW_E_INVAL, "staged chunks pending; flush before disabling");
+    if (epoch_batched && j->has_varchar())
+        FAIL(RW_E_INVAL, "epoch-batched ingest stages 8-byte columns only; "
+                         "not supported with varchar columns");
     j->epoch_ingest = epoch_batched != 0;
+    return RW_OK;
+}
+
+// the device-batch and device-hop entry points move 8-byte words without
+// the arena behind them (rw_stream.h: varchar payload columns)
+#define JOIN_NO_VARCHAR(j, what)                                          \
+    do {                                                                  \
+        if ((j)->has_varchar())                                           \
+            FAIL(RW_E_INVAL, what " is not supported on a join with "     \
+                                  "varchar columns");                     \
+    } while (0)
+
+int rw_hash_join_varlen_reserve(void* h, int side, uint64_t bytes) {
+    auto* j = (HashJoin*)h;
+    if (side != 0 && side != 1) FAIL(RW_E_INVAL, "bad side");
+    if (!j->m.vc_mask[side])
+        FAIL(RW_E_INVAL, "side %d has no varchar column", side);
+    if (j->seen_input)
+        FAIL(RW_E_INVAL, "varlen_reserve is legal only before any input");
+    if (!bytes || bytes > rwvarlen::MAX_OFF)
+        FAIL(RW_E_INVAL, "varlen_reserve: bad capacity");
+    if (j->side[side].arena) {
+        hipFree(j->side[side].arena);
+        j->side[side].arena = nullptr;
+        j->arena_cap[side] = 0;
+    }
+    j->arena_reserve[side] = bytes;
+    return j->arena_ensure(side, 0);
+}
+
+int rw_hash_join_varlen_stats(void* h, int side, uint64_t* used,
+                              uint64_t* capacity) {
+    auto* j = (HashJoin*)h;
+    if (side != 0 && side != 1) FAIL(RW_E_INVAL, "bad side");
+    if (used) *used = j->arena_used[side];
+    if (capacity) *capacity = j->arena_cap[side];
+    return RW_OK;
+}
+
+int rw_hash_join_varlen_emit_stats(void* h, double* ms, double* copy_ms,
+                                   uint64_t* bytes, uint64_t* launches) {
+    auto* j = (HashJoin*)h;
+    if (ms) *ms = j->vemit_ms;
+    if (copy_ms) *copy_ms = j->vcopy_ms;
+    if (bytes) *bytes = j->vemit_bytes;
+    if (launches) *launches = j->vemit_launches;
     return RW_OK;
 }
 
@@ -7411,6 +8087,11 @@ void rw_hash_join_destroy(void* h) { delete (HashJoin*)h; }
 
 void* rw_join_bench_preload(void* h, int side, const RwChunk* c) {
     auto* j = (HashJoin*)h;
+    if (j->has_varchar()) {
+        g_err = "rw_join_bench_preload is not supported on a join with "
+                "varchar columns";
+        return nullptr;
+    }
     auto* b = new JoinBatchDev{};
     uint32_t n = c->n_rows;
     for (int ci = 0; ci < j->m.n_cols[side]; ci++) {
@@ -7440,6 +8121,7 @@ void* rw_join_bench_preload(void* h, int side, const RwChunk* c) {
 // buffer until rw_join_bench_drain
 int rw_join_bench_apply(void* h, int side, void* batch) {
     auto* j = (HashJoin*)h;
+    JOIN_NO_VARCHAR(j, "rw_join_bench_apply");
     return j->probe(side, *(JoinBatchDev*)batch, true, 0,
                     ((JoinBatchDev*)batch)->n_rows);
 }
@@ -7457,6 +8139,7 @@ __global__ void join_counters_reset_kernel(uint32_t* counters) {
 int rw_join_bench_run(void* h, int side, void** batches, int n_batches,
                       int steps) {
     auto* j = (HashJoin*)h;
+    JOIN_NO_VARCHAR(j, "rw_join_bench_run");
     for (int i = 0; i < steps; i++) {
         // the inner probe's per-batch setup re-bases the output block, so
         // no per-step reset is needed; the last step's emissions survive
@@ -7546,6 +8229,7 @@ int rw_join_apply_aggout(void* join_h, void* agg_h, int side,
                          uint64_t n_rows) {
     auto* j = (HashJoin*)join_h;
     auto* agg = (HashAgg*)agg_h;
+    JOIN_NO_VARCHAR(j, "rw_join_apply_aggout");
     if (side != 0 && side != 1) FAIL(RW_E_INVAL, "bad side");
     if (n_map != j->m.n_cols[side])
         FAIL(RW_E_INVAL, "col_map size %d != side cols %d", n_map,
@@ -7581,6 +8265,7 @@ int rw_join_apply_aggout(void* join_h, void* agg_h, int side,
 // rw_join_apply_aggout that want the emissions as chunks (parity tests)
 int rw_join_marshal_output(void* join_h) {
     auto* j = (HashJoin*)join_h;
+    JOIN_NO_VARCHAR(j, "rw_join_marshal_output");
     HIP_TRY(hipStreamSynchronize(j->stream));
     return j->drain_output();
 }
@@ -7594,6 +8279,7 @@ int rw_join_vnode_hop(void* join_h, void* batch, uint32_t col, uint8_t type,
                       uint32_t vnode_count) {
     auto* j = (HashJoin*)join_h;
     auto* b = (JoinBatchDev*)batch;
+    JOIN_NO_VARCHAR(j, "rw_join_vnode_hop");
     if (j->d_vnode_hop_cap < b->n_rows) {
         if (j->d_vnode_hop) hipFree(j->d_vnode_hop);
         HIP_TRY(hipMalloc(&j->d_vnode_hop, (size_t)b->n_rows * 2 + 2));
@@ -7614,6 +8300,7 @@ int rw_join_vnode_hop(void* join_h, void* batch, uint32_t col, uint8_t type,
 int rw_agg_apply_joinout(void* agg_h, void* join_h) {
     auto* agg = (HashAgg*)agg_h;
     auto* j = (HashJoin*)join_h;
+    JOIN_NO_VARCHAR(j, "rw_agg_apply_joinout");
     if (agg->n_dec)
         FAIL(RW_E_INVAL, "decimal columns not yet in the join output block");
     if (hipStreamSynchronize(j->stream) != hipSuccess)
@@ -7696,6 +8383,7 @@ int rw_q7pipe_bench_run(void* agg_h, void* join_h, void** agg_batches,
                         int n_map, int step0) {
     auto* agg = (HashAgg*)agg_h;
     auto* j = (HashJoin*)join_h;
+    JOIN_NO_VARCHAR(j, "rw_q7pipe_bench_run");
     // Long-run state maintenance: the agg change stream retires a right-
     // side record per replaced window max (U- then U+), so dead records
     // accumulate and lengthen the probe walks. Every RW_Q7PIPE_COMPACT
@@ -7802,10 +8490,32 @@ int rw_hash_join_restore(void* h, int side, const uint8_t* buf,
     std::vector<std::vector<uint8_t>> valid(ncols,
                                             std::vector<uint8_t>(n));
     std::vector<uint32_t> degrees(n, 0);
+    // varchar columns: decoded strings as bytes + offsets per column
+    const uint32_t vcm = j->m.vc_mask[side];
+    std::vector<std::vector<uint8_t>> sbytes(ncols);
+    std::vector<std::vector<uint32_t>> soffs(ncols);
+    for (int c = 0; c < ncols; c++)
+        if ((vcm >> c) & 1) soffs[c].assign(1, 0);
     uint32_t i = 0;
     for (auto& [kbytes, val] : merged) {
         size_t off = 0;
         for (int c = 0; c < ncols; c++) {
+            if ((vcm >> c) & 1) {
+                bool null = false;
+                const uint8_t* sp = nullptr;
+                uint32_t slen = 0;
+                size_t got = rwcodec::value_decode_str(
+                    val.data() + off, val.size() - off, &null, &sp, &slen);
+                if (!got) FAIL(RW_E_INVAL, "restore: bad varchar datum");
+                off += got;
+                if (sbytes[c].size() + (uint64_t)slen > UINT32_MAX)
+                    FAIL(RW_E_INVAL, "restore: column %d strings exceed "
+                                     "4 GiB in one call", c);
+                sbytes[c].insert(sbytes[c].end(), sp, sp + slen);
+                soffs[c].push_back((uint32_t)sbytes[c].size());
+                valid[c][i] = !null;
+                continue;
+            }
             rwcodec::DatumC d;
             size_t got = rwcodec::value_decode_datum(
                 val.data() + off, val.size() - off, j->types[side][c], &d);
@@ -7818,14 +8528,45 @@ int rw_hash_join_restore(void* h, int side, const uint8_t* buf,
         if (di != degs.end()) degrees[i] = di->second;
         i++;
     }
-    int rc = j->ensure_stage(side, n);
-    if (rc != RW_OK) return rc;
-    JoinBatchDev b = j->stage[side];
-    for (int c = 0; c < ncols; c++) {
-        HIP_TRY(hipMemcpy(b.col_vals[c], cols[c].data(), (size_t)n * 8,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b.col_valid[c], valid[c].data(), n,
-                          hipMemcpyHostToDevice));
+    j->seen_input = true;
+    int rc;
+    JoinBatchDev b;
+    if (vcm) {
+        // varchar side: the decoded rows go through the upload path, which
+        // appends the strings to the arena and stages reference words
+        std::vector<RwVarlenData> vds(ncols);
+        std::vector<RwColumn> rcols(ncols);
+        std::vector<uint8_t> rops(n, RW_OP_INSERT);
+        for (int c = 0; c < ncols; c++) {
+            rcols[c].type = j->types[side][c];
+            rcols[c].valid = valid[c].data();
+            if ((vcm >> c) & 1) {
+                vds[c] = RwVarlenData{soffs[c].data(), sbytes[c].data()};
+                rcols[c].data = &vds[c];
+            } else {
+                rcols[c].data = cols[c].data();
+            }
+        }
+        RwChunk rch{};
+        rch.n_rows = n;
+        rch.n_cols = (uint32_t)ncols;
+        rch.ops = rops.data();
+        rch.vis = nullptr;
+        rch.cols = rcols.data();
+        rc = j->upload(side, &rch, &b);
+        if (rc != RW_OK) return rc;
+        // the staged host buffers die with this scope
+        HIP_TRY(hipStreamSynchronize(j->stream));
+    } else {
+        rc = j->ensure_stage(side, n);
+        if (rc != RW_OK) return rc;
+        b = j->stage[side];
+        for (int c = 0; c < ncols; c++) {
+            HIP_TRY(hipMemcpy(b.col_vals[c], cols[c].data(), (size_t)n * 8,
+                              hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(b.col_valid[c], valid[c].data(), n,
+                              hipMemcpyHostToDevice));
+        }
     }
     b.vis = nullptr;
     b.n_rows = n;
@@ -7903,8 +8644,89 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
     if (hipStreamSynchronize(j->stream) != hipSuccess)
         FAIL(RW_E_INTERNAL, "compact relink failed");
     j->flush_mark[side] = n_alive;
+    // Rebuild the arena from the live records only (length, scan, copy,
+    // word rewrite per varchar column). Until here the strings of
+    // retracted / watermark-cleaned rows and the bytes appended for delete
+    // rows are garbage that stays allocated.
+    uint64_t arena_freed = 0;
+    if (j->m.vc_mask[side] && sd.arena) {
+        uint8_t* na = nullptr;
+        HIP_TRY(hipMalloc(&na, j->arena_cap[side] +
+                               2 * VARLEN_COPY_PAD * MAX_COLS));
+        uint64_t new_used = 0;
+        int rcv = RW_OK;
+        for (int c = 0; c < j->m.n_cols[side] && rcv == RW_OK && n_alive; c++) {
+            if (!((j->m.vc_mask[side] >> c) & 1)) continue;
+            rcv = j->ensure_vscratch(n_alive);
+            if (rcv != RW_OK) break;
+            VarlenView v{};
+            v.words = (const uint64_t*)(sd.rows + 16) + c;
+            v.stride = sd.row_stride / 8;
+            uint32_t blocks = (n_alive + 1 + 255) / 256;
+            if (blocks > 4096) blocks = 4096;
+            varlen_len_kernel<<<blocks, 256, 0, j->stream>>>(v, n_alive,
+                                                             j->d_vlens);
+            size_t tmp = 0;
+            if (rocprim::exclusive_scan(nullptr, tmp, j->d_vlens, j->d_voffs,
+                                        (uint64_t)0, (size_t)n_alive + 1,
+                                        rocprim::plus<uint64_t>(),
+                                        j->stream) != hipSuccess) {
+                rcv = RW_E_INTERNAL;
+                break;
+            }
+            if (tmp > j->d_scan_tmp_cap) {
+                if (j->d_scan_tmp) hipFree(j->d_scan_tmp);
+                j->d_scan_tmp = nullptr;
+                j->d_scan_tmp_cap = 0;
+                if (hipMalloc(&j->d_scan_tmp, tmp) != hipSuccess) {
+                    rcv = RW_E_INTERNAL;
+                    break;
+                }
+                j->d_scan_tmp_cap = tmp;
+            }
+            uint64_t total = 0;
+            if (rocprim::exclusive_scan(j->d_scan_tmp, tmp, j->d_vlens,
+                                        j->d_voffs, (uint64_t)0,
+                                        (size_t)n_alive + 1,
+                                        rocprim::plus<uint64_t>(),
+                                        j->stream) != hipSuccess ||
+                hipMemcpyAsync(&total, j->d_voffs + n_alive, 8,
+                               hipMemcpyDeviceToHost, j->stream) != hipSuccess ||
+                hipStreamSynchronize(j->stream) != hipSuccess) {
+                rcv = RW_E_INTERNAL;
+                break;
+            }
+            // every live cell owns its bytes in the old arena, so the live
+            // total fits the old capacity; each column's region starts
+            // unit-aligned (the copy stores whole units), which the
+            // allocation's slack covers
+            uint64_t base = (new_used + VARLEN_COPY_PAD - 1) &
+                            ~(uint64_t)(VARLEN_COPY_PAD - 1);
+            if (total)
+                varlen_copy_launch(v, sd.arena, j->d_voffs, n_alive, total,
+                                   na + base, j->stream);
+            uint32_t rblocks = (n_alive + 255) / 256;
+            if (rblocks > 4096) rblocks = 4096;
+            varlen_rewrite_kernel<<<rblocks, 256, 0, j->stream>>>(
+                sd, c, n_alive, j->d_voffs, base);
+            if (hipStreamSynchronize(j->stream) != hipSuccess) {
+                rcv = RW_E_INTERNAL;
+                break;
+            }
+            new_used = base + total;
+        }
+        if (rcv != RW_OK) {
+            hipFree(na);
+            FAIL(RW_E_INTERNAL, "compact: arena rebuild failed");
+        }
+        hipFree(sd.arena);
+        sd.arena = na;
+        if (j->arena_used[side] > new_used)
+            arena_freed = j->arena_used[side] - new_used;
+        j->arena_used[side] = new_used;
+    }
     if (reclaimed)
-        *reclaimed = (uint64_t)(cur - n_alive) * sd.row_stride;
+        *reclaimed = (uint64_t)(cur - n_alive) * sd.row_stride + arena_freed;
     return RW_OK;
 }
 
