@@ -81,7 +81,8 @@ static inline uint32_t rw_type_size(uint8_t t) {
         case RW_T_TS: return 8;
         case RW_T_DECIMAL: return 16;
         /* RW_T_VARCHAR is not fixed width: 0. Code that sizes a column with
-         * this must reject type 7 instead of copying 0 bytes. */
+         * this must handle type 7 on its own (rw_dispatch_compute copies the
+         * RwVarlenData) or reject it, never copy 0 bytes. */
         default: return 0;
     }
 }

@@ -344,6 +344,22 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed);
  *    rw_join_bench_preload/apply/run, and the device hops
  *    rw_join_apply_aggout, rw_join_marshal_output, rw_agg_apply_joinout,
  *    rw_join_vnode_hop, rw_q7pipe_bench_run.
+ *  - The hop IN FRONT of the join carries varchar:
+ *    rw_vnode_compute takes RW_T_VARCHAR dist keys in any mix and position
+ *    with the fixed-width types (a non-NULL string feeds its bytes then one
+ *    0xFF into the CRC; NULL the usual 4-byte sentinel), and
+ *    rw_dispatch_compute carries varchar columns into every output: one
+ *    fresh RwVarlenData per column per output, NULL rows zero length,
+ *    released by rw_chunk_free. Both validate the offsets of every varchar
+ *    column they touch before the first allocation (RW_E_INVAL). The U-pair
+ *    downgrade compares varchar dist-key datums by validity, length, bytes.
+ *    librw_exchange's typed entries (rw_exchange_partition /
+ *    rw_exchange_run_typed, rw_exchange.hip) move them between devices in
+ *    the block layout of include/rw_xpayload.hpp.
+ *    Out of scope: device-resident join ingest of a received payload (the
+ *    join consumes host chunks via push_chunk), varchar in
+ *    rw_agg_apply_payload / HashAgg, rw_join_vnode_hop on a varchar join,
+ *    and the U-pair downgrade inside the device partition.
  *
  * rw_hash_join_varlen_reserve sets `side`'s initial arena capacity in
  * bytes; legal only before any input or restore (RW_E_INVAL otherwise, and

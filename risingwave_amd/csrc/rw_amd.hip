@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <new>
 #include <optional>
 #include <string>
 #include <unordered_set>
@@ -35,6 +36,7 @@
 #include "../../include/rw_codec.hpp"
 #include "../../include/rw_stream.h"
 #include "../../include/rw_varlen.hpp"
+#include "../../include/rw_xpayload.hpp"
 
 #define WAVE 64
 
@@ -4204,6 +4206,11 @@ int rw_agg_stats_reset(void* h) {
 // as hash_datum does (native-endian primitive bytes; NULL = u32 0xfffffff0,
 // array/mod.rs:99) mod vnode_count. Oracle counterpart:
 // oracle/oracle_dispatch.cpp; pinned against zlib.crc32 in tests.
+// A non-NULL varchar datum feeds its bytes followed by one 0xFF byte:
+// hash_datum on a &str is `impl Hash for str`, i.e. Hasher::write_str, whose
+// default is write(bytes) then write_u8(0xff), and crc32fast::Hasher
+// implements only write. So "" feeds the single byte 0xFF and differs from
+// NULL (vnode_varlen_kernel below, include/rw_xpayload.hpp).
 
 __device__ uint32_t g_crc_table[256];
 static bool g_crc_table_init = false;
@@ -4274,6 +4281,74 @@ __global__ void vnode_kernel(VnodeBatch b, int n_keys, uint32_t vnode_count,
     }
 }
 
+// Batches with a varchar dist key take this kernel; vnode_kernel above stays
+// what rw_join_vnode_hop and every fixed-width call launch. The feed of a
+// varchar datum: its bytes, then one 0xFF; NULL is the same
+// 4-byte sentinel as for every type. Slicing-by-8 tables in LDS; T0 of them
+// is the byte table the fixed-width datums go through, as in vnode_kernel.
+__device__ uint32_t g_crc8_table[8 * 256];
+static bool g_crc8_table_init = false;
+
+static int ensure_crc8_table() {
+    if (g_crc8_table_init) return RW_OK;
+    static uint32_t tab[8 * 256];
+    rwx::crc_build_tables(tab);
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_crc8_table), tab, sizeof tab) !=
+        hipSuccess)
+        return RW_E_INTERNAL;
+    g_crc8_table_init = true;
+    return RW_OK;
+}
+
+struct VnodeVarlenBatch {
+    const int64_t* col_vals[MAX_KW];   // fixed-width keys (widened to 8 B)
+    const uint8_t* col_valid[MAX_KW];
+    const uint32_t* col_offs[MAX_KW];  // varchar keys: n_rows + 1 offsets
+    const uint8_t* col_bytes[MAX_KW];  // varchar keys: the byte buffer
+    uint8_t types[MAX_KW];
+    uint32_t n_rows;
+};
+
+__global__ void vnode_varlen_kernel(VnodeVarlenBatch b, int n_keys,
+                                    uint32_t vnode_count, uint16_t* out) {
+    __shared__ uint32_t lut[8 * 256];
+    for (int i = threadIdx.x; i < 8 * 256; i += blockDim.x)
+        lut[i] = g_crc8_table[i];
+    __syncthreads();
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < b.n_rows;
+         r += stride) {
+        uint32_t crc = 0xFFFFFFFFu;
+        for (int k = 0; k < n_keys; k++) {
+            if (!b.col_valid[k][r]) {
+                crc = rwx::crc_feed_u32(lut, crc, rwx::NULL_SENTINEL);
+            } else if (b.types[k] == RW_T_VARCHAR) {
+                uint32_t lo = b.col_offs[k][r], hi = b.col_offs[k][r + 1];
+                crc = rwx::crc_feed_str(lut, crc, b.col_bytes[k] + lo, hi - lo);
+            } else if (b.types[k] == RW_T_I32) { // as vnode_kernel
+                crc = rwx::crc_feed_u32(lut, crc, (uint32_t)b.col_vals[k][r]);
+            } else {
+                crc = rwx::crc_feed_u64(lut, crc, (uint64_t)b.col_vals[k][r]);
+            }
+        }
+        out[r] = (uint16_t)((crc ^ 0xFFFFFFFFu) % vnode_count);
+    }
+}
+
+// frees every device allocation of one call on any exit path
+struct DevAllocs {
+    std::vector<void*> ptrs;
+    ~DevAllocs() {
+        for (void* p : ptrs) hipFree(p);
+    }
+    template <class T>
+    hipError_t alloc(T** out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+        if (e == hipSuccess) ptrs.push_back(*out);
+        return e;
+    }
+};
+
 extern "C" {
 
 typedef struct {
@@ -4282,20 +4357,98 @@ typedef struct {
     uint32_t vnode_count;
 } RwVnodeDesc;
 
+// rw_vnode_compute for a key tuple with at least one varchar column, in any
+// position and any mix with the fixed-width types. Every varchar key
+// column's offsets are validated before the first device allocation.
+static int vnode_compute_varlen(const RwVnodeDesc* d, const RwChunk* chunk,
+                                uint16_t* out) {
+    uint32_t n = chunk->n_rows;
+    for (uint32_t k = 0; k < d->n_keys; k++) {
+        const RwColumn& c = chunk->cols[d->key_indices[k]];
+        if (c.type == RW_T_BOOL || c.type == RW_T_DECIMAL)
+            FAIL(RW_E_INVAL, "vnode key type %d unsupported on GPU", c.type);
+        if (c.type != RW_T_VARCHAR) continue;
+        auto* vd = (const RwVarlenData*)c.data;
+        if (!vd) FAIL(RW_E_INVAL, "varchar vnode key (column %u): no data",
+                      d->key_indices[k]);
+        if (const char* why = rwvarlen::validate_offsets(vd->offsets, n))
+            FAIL(RW_E_INVAL, "varchar vnode key (column %u): %s",
+                 d->key_indices[k], why);
+        if (vd->offsets[n] && !vd->bytes)
+            FAIL(RW_E_INVAL, "varchar vnode key (column %u): bytes is NULL",
+                 d->key_indices[k]);
+    }
+    if (d->vnode_count < 1 || d->vnode_count > 65536)
+        FAIL(RW_E_INVAL, "vnode_count %u (1..65536)", d->vnode_count);
+    if (ensure_crc8_table() != RW_OK) FAIL(RW_E_INTERNAL, "crc table");
+    if (n == 0) return RW_OK;
+    DevAllocs da;
+    VnodeVarlenBatch b{};
+    for (uint32_t k = 0; k < d->n_keys; k++) {
+        const RwColumn& c = chunk->cols[d->key_indices[k]];
+        b.types[k] = c.type;
+        uint8_t* valid;
+        HIP_TRY(da.alloc(&valid, n));
+        HIP_TRY(hipMemcpy(valid, c.valid, n, hipMemcpyHostToDevice));
+        b.col_valid[k] = valid;
+        if (c.type == RW_T_VARCHAR) {
+            auto* vd = (const RwVarlenData*)c.data;
+            uint32_t* offs;
+            uint8_t* bytes;
+            HIP_TRY(da.alloc(&offs, ((size_t)n + 1) * 4));
+            HIP_TRY(da.alloc(&bytes, vd->offsets[n]));
+            HIP_TRY(hipMemcpy(offs, vd->offsets, ((size_t)n + 1) * 4,
+                              hipMemcpyHostToDevice));
+            if (vd->offsets[n])
+                HIP_TRY(hipMemcpy(bytes, vd->bytes, vd->offsets[n],
+                                  hipMemcpyHostToDevice));
+            b.col_offs[k] = offs;
+            b.col_bytes[k] = bytes;
+        } else {
+            int64_t* vals;
+            HIP_TRY(da.alloc(&vals, (size_t)n * 8));
+            if (c.type == RW_T_I32 || c.type == RW_T_F32) {
+                std::vector<int64_t> tmp(n); // widen; hashed at native width
+                for (uint32_t r = 0; r < n; r++)
+                    tmp[r] = (int64_t)(uint32_t)((const uint32_t*)c.data)[r];
+                HIP_TRY(hipMemcpy(vals, tmp.data(), (size_t)n * 8,
+                                  hipMemcpyHostToDevice));
+            } else {
+                HIP_TRY(hipMemcpy(vals, c.data, (size_t)n * 8,
+                                  hipMemcpyHostToDevice));
+            }
+            b.col_vals[k] = vals;
+        }
+    }
+    b.n_rows = n;
+    uint16_t* dout;
+    HIP_TRY(da.alloc(&dout, (size_t)n * 2));
+    uint32_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    vnode_varlen_kernel<<<blocks, 256>>>(b, (int)d->n_keys, d->vnode_count,
+                                         dout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 2, hipMemcpyDeviceToHost));
+    return RW_OK;
+}
+
 int rw_vnode_compute(const RwVnodeDesc* d, const RwChunk* chunk, uint16_t* out) {
     if (!gpu_ok()) FAIL(RW_E_NOGPU, "no GPU visible");
     if (d->n_keys < 1 || d->n_keys > MAX_KW) FAIL(RW_E_INVAL, "n_keys");
     if (ensure_crc_table() != RW_OK) FAIL(RW_E_INTERNAL, "crc table");
     uint32_t n = chunk->n_rows;
+    bool has_varchar = false;
+    for (uint32_t k = 0; k < d->n_keys; k++)
+        if (chunk->cols[d->key_indices[k]].type == RW_T_VARCHAR)
+            has_varchar = true;
+    if (has_varchar) return vnode_compute_varlen(d, chunk, out);
     VnodeBatch b{};
     uint8_t types[4] = {0, 0, 0, 0};
     for (uint32_t k = 0; k < d->n_keys; k++) {
         const RwColumn& c = chunk->cols[d->key_indices[k]];
         types[k] = c.type;
         if (c.type == RW_T_BOOL) FAIL(RW_E_INVAL, "bool vnode key unsupported on GPU");
-        if (c.type == RW_T_VARCHAR)
-            FAIL(RW_E_INVAL, "varchar vnode key (column %u) unsupported",
-                 d->key_indices[k]);
         HIP_TRY(hipMalloc(&b.col_vals[k], (size_t)n * 8));
         HIP_TRY(hipMalloc(&b.col_valid[k], n));
         if (c.type == RW_T_I32 || c.type == RW_T_F32) {
@@ -4338,26 +4491,42 @@ typedef struct {
 // HashDataDispatcher::dispatch_data (dispatch.rs:949-1050): vnodes from the
 // GPU kernel; the tiny per-row visibility/op rewrite is host-side (the
 // device-side dense compaction lives in rw_exchange.hip's partition path).
+// Varchar columns travel too: each output holds a fresh RwVarlenData (copy
+// of offsets and bytes, NULL rows zero length) that rw_chunk_free releases.
+// Every varchar column is validated before the first allocation, and an
+// allocation failure after some outputs were built frees them.
 int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
                         RwChunk** outs) {
     uint32_t n = chunk->n_rows;
-    // the per-output column copies below size by rw_type_size, which is 0
-    // for the variable-width type: dispatch of varchar columns is not built
-    for (uint32_t c = 0; c < chunk->n_cols; c++)
-        if (chunk->cols[c].type == RW_T_VARCHAR)
-            FAIL(RW_E_INVAL, "dispatch of varchar column %u unsupported", c);
+    for (uint32_t c = 0; c < chunk->n_cols; c++) {
+        if (chunk->cols[c].type != RW_T_VARCHAR) continue;
+        auto* vd = (const RwVarlenData*)chunk->cols[c].data;
+        if (!vd) FAIL(RW_E_INVAL, "dispatch: varchar column %u has no data", c);
+        if (const char* why = rwvarlen::validate_offsets(vd->offsets, n))
+            FAIL(RW_E_INVAL, "dispatch: varchar column %u: %s", c, why);
+        if (vd->offsets[n] && !vd->bytes)
+            FAIL(RW_E_INVAL, "dispatch: varchar column %u: bytes is NULL", c);
+    }
     std::vector<uint16_t> vnodes(n);
     int rc = rw_vnode_compute(&d->v, chunk, vnodes.data());
     if (rc != RW_OK) return rc;
 
     std::vector<uint8_t> ops(chunk->ops, chunk->ops + n);
     auto visible = [&](uint32_t r) { return !chunk->vis || chunk->vis[r]; };
-    auto datum_eq_i64 = [&](uint32_t col, uint32_t a, uint32_t b) {
+    auto datum_eq = [&](uint32_t col, uint32_t a, uint32_t b) {
         const RwColumn& c = chunk->cols[col];
         if (c.valid[a] != c.valid[b]) return false;
         if (!c.valid[a]) return true;
         switch (c.type) {
             case RW_T_I32: return ((const int32_t*)c.data)[a] == ((const int32_t*)c.data)[b];
+            case RW_T_VARCHAR: { // validity, length, bytes
+                auto* vd = (const RwVarlenData*)c.data;
+                uint32_t la = vd->offsets[a + 1] - vd->offsets[a];
+                uint32_t lb = vd->offsets[b + 1] - vd->offsets[b];
+                return la == lb &&
+                       (la == 0 || memcmp(vd->bytes + vd->offsets[a],
+                                          vd->bytes + vd->offsets[b], la) == 0);
+            }
             default: return ((const int64_t*)c.data)[a] == ((const int64_t*)c.data)[b];
         }
     };
@@ -4369,7 +4538,7 @@ int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
         } else if (ops[r] == RW_OP_UPDATE_INSERT && last_ud >= 0) {
             bool changed = false;
             for (uint32_t k = 0; k < d->v.n_keys && !changed; k++)
-                changed = !datum_eq_i64(d->v.key_indices[k], (uint32_t)last_ud, r);
+                changed = !datum_eq(d->v.key_indices[k], (uint32_t)last_ud, r);
             if (changed) {
                 ops[last_ud] = RW_OP_DELETE;
                 ops[r] = RW_OP_INSERT;
@@ -4378,30 +4547,73 @@ int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
         }
     }
 
-    for (uint32_t o = 0; o < d->n_outputs; o++) {
-        auto* ch = new RwChunk();
-        auto* cols = new RwColumn[chunk->n_cols];
-        auto* op_arr = new uint8_t[n];
-        auto* vis = new uint8_t[n];
-        memcpy(op_arr, ops.data(), n);
-        for (uint32_t r = 0; r < n; r++)
-            vis[r] = visible(r) && d->vnode_to_output[vnodes[r]] == o ? 1 : 0;
+    uint32_t built = 0;
+    try {
+        // a varchar column's output form, built once: NULL rows zero length
+        std::vector<std::vector<uint32_t>> voffs(chunk->n_cols);
+        std::vector<std::vector<uint8_t>> vbytes(chunk->n_cols);
         for (uint32_t c = 0; c < chunk->n_cols; c++) {
-            uint32_t sz = rw_type_size(chunk->cols[c].type);
-            auto* data = new int64_t[n]; // freed as int64_t* by rw_chunk_free
-            auto* valid = new uint8_t[n];
-            memcpy(data, chunk->cols[c].data, (size_t)n * sz);
-            memcpy(valid, chunk->cols[c].valid, n);
-            cols[c].type = chunk->cols[c].type;
-            cols[c].valid = valid;
-            cols[c].data = data;
+            if (chunk->cols[c].type != RW_T_VARCHAR) continue;
+            auto* vd = (const RwVarlenData*)chunk->cols[c].data;
+            voffs[c].assign((size_t)n + 1, 0);
+            vbytes[c].reserve(vd->offsets[n]);
+            for (uint32_t r = 0; r < n; r++) {
+                if (chunk->cols[c].valid[r])
+                    vbytes[c].insert(vbytes[c].end(),
+                                     vd->bytes + vd->offsets[r],
+                                     vd->bytes + vd->offsets[r + 1]);
+                voffs[c][r + 1] = (uint32_t)vbytes[c].size();
+            }
         }
-        ch->n_rows = n;
-        ch->n_cols = chunk->n_cols;
-        ch->ops = op_arr;
-        ch->vis = vis;
-        ch->cols = cols;
-        outs[o] = ch;
+        for (uint32_t o = 0; o < d->n_outputs; o++) {
+            // the chunk is freeable by rw_chunk_free at every point below
+            auto* ch = new RwChunk();
+            outs[o] = ch;
+            built = o + 1;
+            auto* cols = new RwColumn[chunk->n_cols]();
+            ch->cols = cols;
+            ch->n_rows = n;
+            for (uint32_t c = 0; c < chunk->n_cols; c++) {
+                cols[c].type = chunk->cols[c].type;
+                ch->n_cols = c + 1;
+                auto* valid = new uint8_t[n];
+                cols[c].valid = valid;
+                memcpy(valid, chunk->cols[c].valid, n);
+                if (cols[c].type == RW_T_VARCHAR) {
+                    auto* vd = new RwVarlenData();
+                    vd->offsets = nullptr;
+                    vd->bytes = nullptr;
+                    cols[c].data = vd;
+                    auto* offs = new uint32_t[(size_t)n + 1];
+                    vd->offsets = offs;
+                    memcpy(offs, voffs[c].data(), ((size_t)n + 1) * 4);
+                    auto* bytes = new uint8_t[vbytes[c].size() + 1];
+                    vd->bytes = bytes;
+                    if (!vbytes[c].empty())
+                        memcpy(bytes, vbytes[c].data(), vbytes[c].size());
+                } else {
+                    uint32_t sz = rw_type_size(cols[c].type);
+                    // freed as int64_t* by rw_chunk_free
+                    auto* data = new int64_t[((size_t)n * sz + 7) / 8];
+                    cols[c].data = data;
+                    memcpy(data, chunk->cols[c].data, (size_t)n * sz);
+                }
+            }
+            ch->n_cols = chunk->n_cols;
+            auto* op_arr = new uint8_t[n];
+            ch->ops = op_arr;
+            memcpy(op_arr, ops.data(), n);
+            auto* vis = new uint8_t[n];
+            ch->vis = vis;
+            for (uint32_t r = 0; r < n; r++)
+                vis[r] = visible(r) && d->vnode_to_output[vnodes[r]] == o ? 1 : 0;
+        }
+    } catch (const std::bad_alloc&) {
+        for (uint32_t o = 0; o < built; o++) {
+            rw_chunk_free(outs[o]);
+            outs[o] = nullptr;
+        }
+        FAIL(RW_E_INTERNAL, "dispatch: out of host memory");
     }
     return RW_OK;
 }
