@@ -400,9 +400,8 @@ __device__ __forceinline__ long long* jvals(JoinRowHdr* h) {
 }
 
 // First slot for a join-table probe: TOP bits of the hash, so the slot index
-// is monotone in h and a hash-prefix partition maps to a CONTIGUOUS slot
-// region — the locality lever of the partitioned probe/insert pipeline
-// (jpart_* kernels below). Distribution-equivalent to h & cap_mask.
+// is monotone in h and a hash prefix maps to a CONTIGUOUS slot region.
+// Distribution-equivalent to h & cap_mask; table layout depends on it.
 __device__ __forceinline__ uint32_t jslot_start(uint64_t h, uint32_t cap_mask) {
     return (uint32_t)(h >> (64 - __popc(cap_mask)));
 }
@@ -4026,36 +4025,6 @@ int rw_agg_debug_scan(void* h, RwAggDebug* out) {
     return RW_OK;
 }
 
-// debug: dump dirty_list entries -> (slot, state, key0, acc[0], acc[1])
-int rw_agg_debug_dirty(void* h, uint32_t max_n, uint32_t* slots, uint32_t* states,
-                       int64_t* key0, long long* acc0, long long* acc1,
-                       uint32_t* n_out) {
-    auto* agg = (HashAgg*)h;
-    size_t cap = (size_t)agg->t.cap_mask + 1;
-    hipDeviceSynchronize();
-    uint32_t ctr[3];
-    HIP_TRY(hipMemcpy(ctr, agg->t.counters, 12, hipMemcpyDeviceToHost));
-    uint32_t n = ctr[0] < max_n ? ctr[0] : max_n;
-    std::vector<uint32_t> dl(n);
-    if (n) HIP_TRY(hipMemcpy(dl.data(), agg->t.dirty_list, n * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> st(cap);
-    std::vector<int64_t> keys(cap * agg->KW);
-    std::vector<long long> acc(cap * agg->n_calls);
-    HIP_TRY(hipMemcpy(st.data(), agg->t.state, cap * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(keys.data(), agg->t.keys, cap * agg->KW * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(acc.data(), agg->t.acc, cap * agg->n_calls * 8, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++) {
-        uint32_t sl = dl[i];
-        slots[i] = sl;
-        states[i] = st[sl];
-        key0[i] = keys[(size_t)sl * agg->KW];
-        acc0[i] = acc[sl];
-        acc1[i] = agg->n_calls > 1 ? acc[cap + sl] : 0;
-    }
-    *n_out = n;
-    return RW_OK;
-}
-
 int rw_agg_checkpoint_drain(void* h, uint8_t** buf, uint64_t* len) {
     auto* agg = (HashAgg*)h;
     // memcmp-key order, as the join/topn/dedup drains (rw_stream.h's ordering
@@ -4833,70 +4802,66 @@ __host__ __device__ __forceinline__ bool j_need_degree(uint8_t t, int side) {
            t == RW_JOIN_RIGHT_ANTI || t == RW_JOIN_RIGHT_SEMI;
 }
 
-// emit one output row with per-emission reservation. form bit0 = include
-// the probe side's columns, bit1 = include the matched record's columns;
-// excluded sides are NULL (JoinOutBuilder append_row / _update / _matched,
-// join/builder.rs:153-318).
-__device__ __forceinline__ void jemit_row(JoinOutDev& out, const JoinMeta& m,
-                                          int S, uint8_t op,
-                                          const JoinBatchDev& b, uint32_t r,
-                                          uint32_t match_vb,
-                                          const long long* mv, int form) {
-    uint32_t orow = atomicAdd(&out.counters[0], 1u);
-    if (orow >= out.cap) {
-        atomicExch(&out.counters[1], 1u);
-        return;
-    }
-    out.ops[orow] = op;
+template <bool NT, typename T>
+__device__ __forceinline__ void jout_store(T* p, T v) {
+    if (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
+// The one output-row writer of the join: every emission stores its row
+// through here. Writes row `orow`: probe-side cells from batch row r, match-side
+// cells through the caller's accessor mval(col) — rec_sel over a
+// register-resident record (a dynamic index into the private copy would
+// demote it to scratch), a plain mv[col], or an sc1 load —
+// validity from match_vb. form bit0 = include the probe side's columns,
+// bit1 = include the matched record's columns; excluded sides are NULL
+// (JoinOutBuilder append_row / _update / _matched, join/builder.rs:153-318).
+// NT = nontemporal stores for ops, values and nulls alike: pre-assigned
+// rows are written once and only read by later launches, and regular
+// stores pay a read-for-ownership line fetch per partial write.
+template <bool NT, typename MVal>
+__device__ __forceinline__ void jwrite_row(JoinOutDev& out, const JoinMeta& m,
+                                           int S, uint8_t op,
+                                           const JoinBatchDev& b, uint32_t r,
+                                           bool dense, uint32_t match_vb,
+                                           MVal mval, int form,
+                                           uint32_t orow) {
+    jout_store<NT>(&out.ops[orow], op);
     for (int c = 0; c < m.n_out; c++) {
         bool from_probe = (int)m.out_src[c] == S;
         uint8_t col = m.out_col[c];
         int64_t v = 0;
         uint8_t valid = 0;
         if (from_probe && (form & 1)) {
-            valid = b.col_valid[col][r];
+            valid = dense || b.col_valid[col][r];
             v = b.col_vals[col][r];
         } else if (!from_probe && (form & 2)) {
             valid = (match_vb >> col) & 1;
-            v = mv[col];
+            v = mval(col);
         }
-        out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-        out.nulls[(size_t)c * out.cap + orow] = !valid;
+        jout_store<NT>(&out.vals[(size_t)c * out.cap + orow],
+                       valid ? v : (int64_t)0);
+        jout_store<NT>(&out.nulls[(size_t)c * out.cap + orow],
+                       (uint8_t)!valid);
     }
 }
 
-// jemit_row over a REGISTER-RESIDENT match record (see the register walk
-// in join_probe_kernel): match values come from the register copy via
-// unrolled selects — a dynamic index into a private array would demote
-// it to scratch and defeat the single-fetch walk.
-__device__ __forceinline__ void jemit_row_rec(JoinOutDev& out,
-                                              const JoinMeta& m, int S,
-                                              uint8_t op,
-                                              const JoinBatchDev& b,
-                                              uint32_t r, uint32_t match_vb,
-                                              const long long* recv,
-                                              int form) {
+// emit one output row with per-emission reservation (plain stores); the
+// match-side accessor is the caller's, as for jwrite_row
+template <typename MVal>
+__device__ __forceinline__ void jemit_row(JoinOutDev& out, const JoinMeta& m,
+                                          int S, uint8_t op,
+                                          const JoinBatchDev& b, uint32_t r,
+                                          uint32_t match_vb, MVal mval,
+                                          int form) {
     uint32_t orow = atomicAdd(&out.counters[0], 1u);
     if (orow >= out.cap) {
         atomicExch(&out.counters[1], 1u);
         return;
     }
-    out.ops[orow] = op;
-    for (int c = 0; c < m.n_out; c++) {
-        bool from_probe = (int)m.out_src[c] == S;
-        uint8_t col = m.out_col[c];
-        int64_t v = 0;
-        uint8_t valid = 0;
-        if (from_probe && (form & 1)) {
-            valid = b.col_valid[col][r];
-            v = b.col_vals[col][r];
-        } else if (!from_probe && (form & 2)) {
-            valid = (match_vb >> col) & 1;
-            v = rec_sel(recv, col);
-        }
-        out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-        out.nulls[(size_t)c * out.cap + orow] = !valid;
-    }
+    jwrite_row<false>(out, m, S, op, b, r, false, match_vb, mval, form, orow);
 }
 
 // own-side insert/delete (join/hash_join.rs:591-681 without the LRU tier)
@@ -4907,7 +4872,7 @@ __device__ __forceinline__ void jown_insert(JoinSideDev own, const JoinMeta& m,
                                             uint32_t init_deg) {
     // wave-aggregated row reservation: the single cursor sustains only
     // ~2.1 G same-line atomicAdds/s, so 1M per-lane adds cost ~0.47 ms per
-    // launch (measured via RW_JOIN_SKIP) — one leader add per wave instead
+    // launch (measured) — one leader add per wave instead
     uint64_t wmask = __ballot(true); // lanes currently inserting
     int lane = threadIdx.x & 63;
     int leader = 63 - __clzll(wmask);
@@ -5000,10 +4965,14 @@ __device__ void join_probe_row_noninner(const JoinBatchDev& b, JoinSideDev own,
     bool outer_self = j_is_outer_side(T, S);
     bool only_fwd_m = j_only_forward_matched_side(T, S);
     bool outer_null = j_outer_side_null(T, S);
+    // the probe row alone, match side NULL
+    auto forward = [&]() {
+        jemit_row(out, m, S, op, b, r, 0, [](int) { return 0LL; }, 1);
+    };
     if (never_match) {
         // null-safe NeverMatch forwards for anti/outer (hash_join.rs:1143-1152)
         if ((anti && fwd_once) || outer_self)
-            jemit_row(out, m, S, op, b, r, 0, nullptr, 1);
+            forward();
         return; // no state write
     }
     uint32_t mhead =
@@ -5071,10 +5040,13 @@ __device__ void join_probe_row_noninner(const JoinBatchDev& b, JoinSideDev own,
                 }
                 auto emit2 = [&](uint8_t op2, int form) {
                     if (regw)
-                        jemit_row_rec(out, m, S, op2, b, r, vb, rec + 2,
-                                      form);
+                        jemit_row(out, m, S, op2, b, r, vb,
+                                  [&](int col) { return rec_sel(rec + 2, col); },
+                                  form);
                     else
-                        jemit_row(out, m, S, op2, b, r, vb, jvals(h), form);
+                        jemit_row(out, m, S, op2, b, r, vb,
+                                  [&](int col) { return jvals(h)[col]; },
+                                  form);
                 };
                 if (is_insert) {
                     if (anti) {
@@ -5106,10 +5078,10 @@ __device__ void join_probe_row_noninner(const JoinBatchDev& b, JoinSideDev own,
     if (my_deg == 0) {
         // forward_if_not_matched (join/builder.rs:303-312)
         if ((anti && fwd_once) || outer_self)
-            jemit_row(out, m, S, op, b, r, 0, nullptr, 1);
+            forward();
     } else if (semi && fwd_once) {
         // forward_exactly_once_if_matched (join/builder.rs:287-300)
-        jemit_row(out, m, S, op, b, r, 0, nullptr, 1);
+        forward();
     }
     if (is_insert)
         jown_insert(own, m, S, b, r, kw, nullmask, out, my_deg);
@@ -5151,7 +5123,7 @@ __global__ void join_count_emitted_kernel(const uint8_t* ops, uint32_t n,
 // launch bounds instead of spilling the inner kernel.
 __global__ __launch_bounds__(256, 4) void join_probe_noninner_kernel(
     JoinBatchDev b, JoinSideDev own, JoinSideDev match, JoinMeta m, int S,
-    JoinOutDev out, uint32_t r0, uint32_t r1, int dbg_skip) {
+    JoinOutDev out, uint32_t r0, uint32_t r1) {
     uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t r = r0 + blockIdx.x * blockDim.x + threadIdx.x; r < r1;
          r += stride) {
@@ -5168,16 +5140,14 @@ __global__ __launch_bounds__(256, 4) void join_probe_noninner_kernel(
             nullmask |= (!valid) << i;
         }
         bool never_match = (nullmask & ~(uint32_t)m.null_safe_mask) != 0;
-        if (!(dbg_skip & 2))
-            join_probe_row_noninner(b, own, match, m, S, out, r, is_insert,
-                                    op, kw, nullmask, never_match);
+        join_probe_row_noninner(b, own, match, m, S, out, r, is_insert, op,
+                                kw, nullmask, never_match);
     }
 }
 
 __global__ __launch_bounds__(256, 6) void join_probe_kernel(
     JoinBatchDev b, JoinSideDev own, JoinSideDev match, JoinMeta m, int S,
-    JoinOutDev out, uint32_t r0, uint32_t r1, const uint32_t* row_base,
-    int dbg_skip = 0) {
+    JoinOutDev out, uint32_t r0, uint32_t r1, const uint32_t* row_base) {
     uint32_t stride = gridDim.x * blockDim.x;
     uint32_t n = r1 - r0;
     uint32_t iters = (n + stride - 1) / stride;
@@ -5222,8 +5192,7 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
         if (active) {
             h64 = hash_key(kw, nullmask, m.KW);
             mhead = jbucket_head(match, h64, m.append_only != 0);
-            if (mhead != UINT32_MAX && !m.append_only && !(dbg_skip & 16)) {
-                // dbg 16 = hash+slot only (stage isolation: no record walk)
+            if (mhead != UINT32_MAX && !m.append_only) {
                 uint32_t row = mhead;
                 // REGISTER-RESIDENT walk (narrow records, 16-B-aligned
                 // stride): each record is fetched ONCE as wide b128 loads
@@ -5233,9 +5202,8 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
                 // 4-MB XCD L2) evict a line between a record's `alive`
                 // check and its key loads; PMC measured ~323 B fetched per
                 // 64-B record (gpurun_out/pmcW67.txt) vs the one-line 128-B
-                // model. dbg 32 forces the legacy field walk for A/B.
-                if (match.row_stride <= 64 && !(match.row_stride & 15) &&
-                    !(dbg_skip & 32)) {
+                // model. Records wider than 64 B keep the field walk.
+                if (match.row_stride <= 64 && !(match.row_stride & 15)) {
                     int nw16 = (int)(match.row_stride >> 4);
                     while (row != UINT32_MAX) {
                         const long long* rp =
@@ -5289,8 +5257,9 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
             // output slot r (ops sentinel 0xFF marks empty slots; the host
             // compacts at drain); matches 2..k append past n via a
             // PER-LANE atomic on the rare multi-match lanes. NO cross-lane
-            // ops: the q8-shape ladder measured ANY wave-convergent
-            // reservation (ballot or shuffle scan) at +135-155 us per 1M
+            // ops: the q8-shape ladder measured ANY
+            // wave-convergent reservation (ballot or shuffle scan) at
+            // +135-155 us per 1M
             // rows — the convergence stalls the wave on its slowest lane's
             // dependent loads — while the pre-assigned form runs at the
             // random-access ceiling (profiles/r02_membw_probes.json).
@@ -5301,79 +5270,28 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
                 if (extra_base + my_n - 1 > out.cap)
                     atomicExch(&out.counters[1], 1u); // overflow
             }
-            if (my_n == 1 && !(dbg_skip & 1) && rec_match) {
+            // All three branches store NONTEMPORAL through jwrite_row.
+            // (Measured store-policy A/B on the single-match emit: full NT
+            // 0.251 ms/step against 0.255 both fully cached and with only
+            // the values NT — a narrow win; the dense orow=r layout
+            // coalesces well under every policy.)
+            if (my_n == 1 && rec_match) {
                 // SINGLE-PASS emission from the REGISTER-RESIDENT match
                 // (the walk's last-loaded record): zero record re-reads.
-                // Store policy A/B (dbg 8 = fully cached, dbg 256 = vals
-                // NT + 1-byte ops/nulls cached): measured 0.251 / 0.255 /
-                // 0.255 ms/step — full NT is the (narrow) winner, the
-                // dense orow=r layout coalesces well under every policy.
-                uint32_t orow = my_base;
-                uint32_t mvb = (uint32_t)(uint64_t)rec[1];
-                bool nt_vals = !(dbg_skip & 8);
-                bool nt_meta = !(dbg_skip & (8 | 256));
-                if (nt_meta)
-                    __builtin_nontemporal_store(op, &out.ops[orow]);
-                else
-                    out.ops[orow] = op;
-                for (int c = 0; c < m.n_out; c++) {
-                    bool from_probe = (int)m.out_src[c] == S;
-                    uint8_t col = m.out_col[c];
-                    int64_t v;
-                    uint8_t valid;
-                    if (from_probe) {
-                        valid = dense || b.col_valid[col][r];
-                        v = b.col_vals[col][r];
-                    } else {
-                        valid = (mvb >> col) & 1;
-                        v = rec_sel(rec + 2, col);
-                    }
-                    if (nt_vals)
-                        __builtin_nontemporal_store(
-                            valid ? v : 0,
-                            &out.vals[(size_t)c * out.cap + orow]);
-                    else
-                        out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-                    if (nt_meta)
-                        __builtin_nontemporal_store(
-                            (uint8_t)!valid,
-                            &out.nulls[(size_t)c * out.cap + orow]);
-                    else
-                        out.nulls[(size_t)c * out.cap + orow] =
-                            (uint8_t)!valid;
-                }
-            } else if (my_n == 1 && !(dbg_skip & 1)) {
+                jwrite_row<true>(
+                    out, m, S, op, b, r, dense, (uint32_t)(uint64_t)rec[1],
+                    [&](int col) { return rec_sel(rec + 2, col); }, 3,
+                    my_base);
+            } else if (my_n == 1) {
                 // SINGLE-PASS emission for the dominant <=1-match case:
                 // the count walk already identified the row — no re-walk
                 JoinRowHdr* h = jrow(match, matched_row);
-                uint32_t orow = my_base;
                 const long long* mv = jvals(h);
-                __builtin_nontemporal_store(op, &out.ops[orow]);
-                for (int c = 0; c < m.n_out; c++) {
-                    bool from_probe = (int)m.out_src[c] == S;
-                    uint8_t col = m.out_col[c];
-                    int64_t v;
-                    uint8_t valid;
-                    if (from_probe) {
-                        valid = dense || b.col_valid[col][r];
-                        v = b.col_vals[col][r];
-                    } else {
-                        valid = (h->validbits >> col) & 1;
-                        v = mv[col];
-                    }
-                    __builtin_nontemporal_store(
-                        valid ? v : 0, &out.vals[(size_t)c * out.cap + orow]);
-                    __builtin_nontemporal_store(
-                        (uint8_t)!valid,
-                        &out.nulls[(size_t)c * out.cap + orow]);
-                }
-            } else if (my_n && !(dbg_skip & 1) &&
-                !(my_n > 1 && extra_base + my_n - 1 > out.cap)) {
-                // second walk: emit (JoinStreamChunkBuilder::append_row).
-                // Emit stores are NONTEMPORAL: the rows are written once
-                // and only read by later launches, and regular stores pay
-                // a read-for-ownership line fetch per partial write
-                // (RW_JOIN_NT_OFF=1 re-measures the cached variant).
+                jwrite_row<true>(
+                    out, m, S, op, b, r, dense, h->validbits,
+                    [&](int col) { return mv[col]; }, 3, my_base);
+            } else if (my_n && !(extra_base + my_n - 1 > out.cap)) {
+                // second walk: emit (JoinStreamChunkBuilder::append_row)
                 uint32_t row = mhead;
                 uint32_t k = 0;
                 while (row != UINT32_MAX && k < my_n) {
@@ -5382,55 +5300,19 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
                         jhdr_key_eq(h, m.key_cols[1 - S], m.KW, kw, nullmask,
                                     false) &&
                         join_cond_ok(m, S, b, r, h->validbits, jvals(h))) {
-                        uint32_t orow = k == 0 ? my_base
-                                               : extra_base + k - 1;
                         const long long* mv = jvals(h);
-                        if (dbg_skip & 8) {
-                            out.ops[orow] = op;
-                            for (int c = 0; c < m.n_out; c++) {
-                                bool from_probe = (int)m.out_src[c] == S;
-                                uint8_t col = m.out_col[c];
-                                int64_t v;
-                                uint8_t valid;
-                                if (from_probe) {
-                                    valid = b.col_valid[col][r];
-                                    v = b.col_vals[col][r];
-                                } else {
-                                    valid = (h->validbits >> col) & 1;
-                                    v = mv[col];
-                                }
-                                out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-                                out.nulls[(size_t)c * out.cap + orow] = !valid;
-                            }
-                        } else {
-                            __builtin_nontemporal_store(op, &out.ops[orow]);
-                            for (int c = 0; c < m.n_out; c++) {
-                                bool from_probe = (int)m.out_src[c] == S;
-                                uint8_t col = m.out_col[c];
-                                int64_t v;
-                                uint8_t valid;
-                                if (from_probe) {
-                                    valid = b.col_valid[col][r];
-                                    v = b.col_vals[col][r];
-                                } else {
-                                    valid = (h->validbits >> col) & 1;
-                                    v = mv[col];
-                                }
-                                __builtin_nontemporal_store(
-                                    valid ? v : 0,
-                                    &out.vals[(size_t)c * out.cap + orow]);
-                                __builtin_nontemporal_store(
-                                    (uint8_t)!valid,
-                                    &out.nulls[(size_t)c * out.cap + orow]);
-                            }
-                        }
+                        jwrite_row<true>(
+                            out, m, S, op, b, r, dense, h->validbits,
+                            [&](int col) { return mv[col]; }, 3,
+                            k == 0 ? my_base : extra_base + k - 1);
                         k++;
                     }
                     row = h->next;
                 }
             }
         } else if (active && mhead != UINT32_MAX) {
-            // append-only path: <=1 match; sc1 reads, per-match atomics
+            // append-only path: <=1 match; sc1 reads, per-match atomics,
+            // plain stores
             uint32_t row = mhead;
             while (row != UINT32_MAX) {
                 JoinRowHdr* h = jrow(match, row);
@@ -5439,28 +5321,12 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
                     jhdr_key_eq(h, m.key_cols[1 - S], m.KW, kw, nullmask,
                                 true) &&
                     join_cond_ok(m, S, b, r, vb, jvals(h))) {
-                    uint32_t orow = atomicAdd(&out.counters[0], 1u);
-                    if (orow >= out.cap) {
-                        atomicExch(&out.counters[1], 1u);
-                    } else {
-                        out.ops[orow] = op;
-                        const long long* mv = jvals(h);
-                        for (int c = 0; c < m.n_out; c++) {
-                            bool from_probe = (int)m.out_src[c] == S;
-                            uint8_t col = m.out_col[c];
-                            int64_t v;
-                            uint8_t valid;
-                            if (from_probe) {
-                                valid = b.col_valid[col][r];
-                                v = b.col_vals[col][r];
-                            } else {
-                                valid = (vb >> col) & 1;
-                                v = (int64_t)ld_i64((const int64_t*)&mv[col]);
-                            }
-                            out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-                            out.nulls[(size_t)c * out.cap + orow] = !valid;
-                        }
-                    }
+                    const long long* mv = jvals(h);
+                    jemit_row(out, m, S, op, b, r, vb,
+                              [&](int col) {
+                                  return ld_i64((const int64_t*)&mv[col]);
+                              },
+                              3);
                     matched_row = row;
                 }
                 row = ld_u32(&h->next);
@@ -5471,13 +5337,10 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
             // PRE-ASSIGNED record slot (row_base + r): inserting rows write
             // their record and link the bucket; every other row marks its
             // slot dead (walks and drains skip by `alive`). No cross-lane
-            // cursor — see the emission comment above. dbg 64 = skip this
-            // whole section (stage isolation: clean walk timing without
-            // the pre-kill store pass the production path replaces with
-            // full record writes).
-            if (r < r1 && !(dbg_skip & 64)) {
+            // cursor — see the emission comment above.
+            if (r < r1) {
                 uint32_t myrow = *row_base + r;
-                bool do_insert = active && !(dbg_skip & 2) && is_insert;
+                bool do_insert = active && is_insert;
                 if (myrow < own.row_cap) {
                     JoinRowHdr* hd2 = jrow(own, myrow);
                     if (do_insert) {
@@ -5520,12 +5383,12 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
                         hd2->alive = 0;
                     }
                 }
-                if (active && !(dbg_skip & 2) && !is_insert)
+                if (active && !is_insert)
                     jown_delete(own, m, S, b, r, kw, nullmask);
             }
             continue;
         }
-        if (!active || (dbg_skip & 2)) continue;
+        if (!active) continue;
 
         if (m.append_only && is_insert && matched_row != UINT32_MAX) {
             // append-only optimize (hash_join.rs:1241-1245)
@@ -5543,482 +5406,6 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
         else
             jown_delete(own, m, S, b, r, kw, nullmask);
     }
-}
-
-// ============ Partitioned probe/insert pipeline (q8 hot path) ============
-//
-// The round-1 single-kernel path was random-access-bound: each probe row
-// touched ~3 random 64-B lines spread over GBs of slot table + record
-// store (PMC: 500–1000 B fetched per row vs the 128-B algorithmic model,
-// profiles/r01_q8_pmc_fetch.txt), sustaining ~2 G own-side inserts/s.
-// This pipeline partitions an all-Insert unique-key batch by the TOP
-// JPART_LOG2 bits of the join-key hash. jslot_start() derives slot
-// indices from the same top bits, so partition p's slots are the
-// CONTIGUOUS window [p*cap/P, (p+1)*cap/P) of BOTH sides' tables, and its
-// records land in one contiguous row-store run per batch (the scatter
-// writes each record into its FINAL row-store position). The fused
-// probe+insert phase runs one workgroup per partition: its slot window
-// (~cap*64/P bytes) stays in the XCD's L2 and its match-record reads fall
-// in per-batch partition runs — DRAM-row-local instead of uniformly
-// random. eq_join_oneside semantics are unchanged (inner join, all
-// visible rows Insert, keys pairwise distinct — the host gates on exactly
-// the conditions under which batch-parallel insert+probe commutes with
-// the reference's sequential per-row loop; hash_join.rs:949-1075).
-//
-// Phases (stream-ordered, no host round-trip):
-//   1. jpart_count          per-block LDS histograms of partition ids
-//   2. jpart_scan           scatter bases + partition ranges + row-store
-//                           reservation (single workgroup)
-//   3. jpart_scatter        write final row records, partition-clustered
-//   4. jpart_probe_insert   per partition: probe match side + emit, then
-//                           link own-side chains (plain RMW — unique keys
-//                           give every touched slot exactly one writer)
-
-#define JPART_LOG2 12
-#define JPART_P (1u << JPART_LOG2)
-#define JPART_NBLK 256
-#define JPART_MIN_ROWS 131072u
-
-__device__ __forceinline__ uint32_t jpart_of(uint64_t h) {
-    return (uint32_t)(h >> (64 - JPART_LOG2));
-}
-
-// per-row key extraction from the input batch; returns false for rows that
-// carry no state (invisible is excluded by the host gate; never-match NULL
-// keys are not inserted and emit nothing under inner join,
-// hash_join.rs:1004-1016)
-__device__ __forceinline__ bool jpart_row_key(const JoinBatchDev& b,
-                                              const JoinMeta& m, int S,
-                                              uint32_t r, int64_t* kw,
-                                              uint32_t* nullmask) {
-    uint32_t nm = 0;
-    for (int i = 0; i < m.KW; i++) {
-        uint8_t col = m.key_cols[S][i];
-        bool valid = b.col_valid[col][r];
-        kw[i] = valid ? b.col_vals[col][r] : 0;
-        nm |= (uint32_t)(!valid) << i;
-    }
-    *nullmask = nm;
-    return !(nm & ~(uint32_t)m.null_safe_mask);
-}
-
-// one counter per 64-B line: same-line atomics from different CUs
-// serialize at the line's home (~12.6 ns each, round-1 measurement)
-#define JPART_PAD 16
-
-__global__ __launch_bounds__(1024) void jpart_count_kernel(
-    JoinBatchDev b, JoinMeta m, int S, uint32_t* ptot) {
-    // LDS histogram per block at 1024 threads (4 waves/SIMD — the
-    // 256-thread variant ran 1 wave/SIMD and was latency-bound), then one
-    // global add per nonzero partition per block (~450K adds total).
-    __shared__ uint32_t hist[JPART_P];
-    for (uint32_t i = threadIdx.x; i < JPART_P; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-    uint32_t n = b.n_rows;
-    uint32_t stride = gridDim.x * blockDim.x;
-    int64_t kw[MAX_KW];
-    uint32_t nm;
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n;
-         r += stride) {
-        if (!jpart_row_key(b, m, S, r, kw, &nm)) continue;
-        atomicAdd(&hist[jpart_of(hash_key(kw, nm, m.KW))], 1u);
-    }
-    __syncthreads();
-    for (uint32_t p = threadIdx.x; p < JPART_P; p += blockDim.x)
-        if (hist[p]) atomicAdd(&ptot[(size_t)p * JPART_PAD], hist[p]);
-}
-
-// single-workgroup scan: per-partition totals → exclusive bases; rewrites
-// pcount[blk][p] into per-block scatter bases; reserves the batch's row
-// range on the device cursor (err code 3 = row store full, as the
-// wave-aggregated reservation in jown_insert)
-__global__ void jpart_scan_kernel(uint32_t* ptot, uint32_t* pcur,
-                                  uint32_t* part_base, uint32_t* row_cursor,
-                                  uint32_t row_cap, uint32_t* row_base,
-                                  uint32_t* err) {
-    __shared__ uint32_t tot[JPART_P];
-    __shared__ uint32_t excl[JPART_P];
-    for (uint32_t p = threadIdx.x; p < JPART_P; p += blockDim.x) {
-        uint32_t s = ptot[(size_t)p * JPART_PAD];
-        ptot[(size_t)p * JPART_PAD] = 0; // ready for the next batch
-        tot[p] = s;
-        excl[p] = s;
-    }
-    __syncthreads();
-    // Hillis-Steele inclusive scan over excl[]
-    for (uint32_t off = 1; off < JPART_P; off <<= 1) {
-        uint32_t v[JPART_P / 1024];
-        for (uint32_t i = threadIdx.x, k = 0; i < JPART_P;
-             i += blockDim.x, k++)
-            v[k] = i >= off ? excl[i - off] : 0;
-        __syncthreads();
-        for (uint32_t i = threadIdx.x, k = 0; i < JPART_P;
-             i += blockDim.x, k++)
-            excl[i] += v[k];
-        __syncthreads();
-    }
-    uint32_t total = excl[JPART_P - 1];
-    if (threadIdx.x == 0) {
-        uint32_t base = atomicAdd(row_cursor, total);
-        if ((uint64_t)base + total > row_cap) atomicExch(err, 3u);
-        *row_base = base;
-        part_base[JPART_P] = total;
-    }
-    __syncthreads();
-    for (uint32_t p = threadIdx.x; p < JPART_P; p += blockDim.x) {
-        uint32_t base = excl[p] - tot[p]; // exclusive base of partition p
-        part_base[p] = base;
-        pcur[(size_t)p * JPART_PAD] = base; // scatter cursors
-    }
-}
-
-__global__ void jpart_scatter_kernel(JoinBatchDev b, JoinMeta m, int S,
-                                     JoinSideDev own, uint32_t* pcur,
-                                     const uint32_t* row_base,
-                                     const uint32_t* err) {
-    if (*err) return;
-    uint32_t rb = *row_base;
-    uint32_t n = b.n_rows;
-    uint32_t stride = gridDim.x * blockDim.x;
-    int64_t kw[MAX_KW];
-    uint32_t nm;
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n;
-         r += stride) {
-        if (!jpart_row_key(b, m, S, r, kw, &nm)) continue;
-        uint32_t p = jpart_of(hash_key(kw, nm, m.KW));
-        uint32_t row = rb + atomicAdd(&pcur[(size_t)p * JPART_PAD], 1u);
-        // final row record, built in registers and stored with 16-B vector
-        // writes (plain cached stores: the next kernel on the stream
-        // observes them through the inter-dispatch cache flush)
-        JoinRowHdr* hd = jrow(own, row);
-        long long vals[MAX_COLS];
-        uint32_t vb = 0;
-        int nc = m.n_cols[S];
-        for (int c = 0; c < nc; c++) {
-            vals[c] = b.col_vals[c][r];
-            vb |= (uint32_t)(b.col_valid[c][r] != 0) << c;
-        }
-        ulonglong2* dst = (ulonglong2*)hd;
-        ulonglong2 h0;
-        h0.x = ((uint64_t)UINT32_MAX << 32) | 1u;        // alive=1, next=~0
-        h0.y = (uint64_t)vb;                              // validbits, degree=0
-        dst[0] = h0;
-        int c = 0;
-        for (; c + 1 < nc; c += 2) {
-            ulonglong2 v;
-            v.x = (uint64_t)vals[c];
-            v.y = (uint64_t)vals[c + 1];
-            dst[1 + c / 2] = v;
-        }
-        if (c < nc) jvals(hd)[c] = vals[c];
-    }
-}
-
-// inner-join condition over a probe ROW RECORD (vs join_cond_ok's batch row)
-__device__ __forceinline__ bool jpart_cond_ok(const JoinMeta& m, int S,
-                                              const long long* pv,
-                                              uint32_t pvb, uint32_t mvb,
-                                              const long long* mv) {
-    for (int ci = 0; ci < m.n_cond; ci++) {
-        auto& cd = m.cond[ci];
-        auto fetch = [&](uint8_t src, uint8_t col, int64_t* v) -> bool {
-            if ((int)src == S) {
-                if (!((pvb >> col) & 1)) return false;
-                *v = pv[col];
-            } else {
-                if (!((mvb >> col) & 1)) return false;
-                *v = mv[col];
-            }
-            return true;
-        };
-        int64_t a, c;
-        if (!fetch(cd.src_l, cd.col_l, &a)) return false;
-        if (!fetch(cd.src_r, cd.col_r, &c)) return false;
-        c += cd.rconst;
-        bool ok;
-        switch (cd.op) {
-            case RW_CMP_LT: ok = a < c; break;
-            case RW_CMP_LE: ok = a <= c; break;
-            case RW_CMP_GT: ok = a > c; break;
-            case RW_CMP_GE: ok = a >= c; break;
-            default: ok = false;
-        }
-        if (!ok) return false;
-    }
-    return true;
-}
-
-__global__ __launch_bounds__(256, 8) void jpart_probe_insert_kernel(
-    JoinSideDev own, JoinSideDev match, JoinMeta m, int S, JoinOutDev out,
-    const uint32_t* part_base, const uint32_t* row_base,
-    const uint32_t* err) {
-    if (*err) return;
-    uint32_t rb = *row_base;
-    uint32_t lo = part_base[blockIdx.x];
-    uint32_t hi = part_base[blockIdx.x + 1]; // [JPART_P] holds the total
-    int lane = threadIdx.x & 63;
-    uint32_t n = hi - lo;
-    uint32_t iters = (n + blockDim.x - 1) / blockDim.x;
-    for (uint32_t it = 0; it < iters; it++) {
-        uint32_t i = it * blockDim.x + threadIdx.x;
-        bool active = i < n;
-        uint32_t row = rb + lo + i;
-        int64_t kw[MAX_KW];
-        uint32_t nm = 0;
-        JoinRowHdr* hd = nullptr;
-        long long* hv = nullptr;
-        uint32_t pvb = 0;
-        if (active) {
-            hd = jrow(own, row);
-            hv = jvals(hd);
-            pvb = hd->validbits;
-            for (int k = 0; k < m.KW; k++) {
-                uint8_t col = m.key_cols[S][k];
-                bool valid = (pvb >> col) & 1;
-                kw[k] = valid ? hv[col] : 0;
-                nm |= (uint32_t)(!valid) << k;
-            }
-        }
-        // probe the match side (immutable during this launch: the batch
-        // mutates only `own`)
-        uint32_t mhead = UINT32_MAX;
-        uint32_t my_n = 0;
-        if (active) {
-            mhead = jbucket_head(match, hash_key(kw, nm, m.KW), false);
-            uint32_t mr = mhead;
-            while (mr != UINT32_MAX) {
-                JoinRowHdr* mh = jrow(match, mr);
-                if (mh->alive &&
-                    jhdr_key_eq(mh, m.key_cols[1 - S], m.KW, kw, nm, false) &&
-                    jpart_cond_ok(m, S, hv, pvb, mh->validbits, jvals(mh)))
-                    my_n++;
-                mr = mh->next;
-            }
-        }
-        // wave-aggregated output reservation + emit (multiset parity; the
-        // reference's intra-epoch order is nondeterministic)
-        // ballot fast path for my_n<=1 (see join_probe_kernel)
-        uint64_t multi = __ballot(my_n > 1);
-        uint32_t total, my_base;
-        uint32_t base = 0;
-        if (!multi) {
-            uint64_t got = __ballot(my_n != 0);
-            total = (uint32_t)__popcll(got);
-            if (lane == 0 && total) base = atomicAdd(&out.counters[0], total);
-            base = (uint32_t)__shfl((int)base, 0);
-            my_base = base + (uint32_t)__popcll(got & ((1ULL << lane) - 1));
-        } else {
-            uint32_t incl = my_n;
-            for (int d = 1; d < 64; d <<= 1) {
-                uint32_t o = __shfl_up(incl, d);
-                if (lane >= d) incl += o;
-            }
-            total = (uint32_t)__shfl((int)incl, 63);
-            if (lane == 0 && total) base = atomicAdd(&out.counters[0], total);
-            base = (uint32_t)__shfl((int)base, 0);
-            my_base = base + incl - my_n;
-        }
-        if (total && base + total > out.cap) {
-            if (lane == 0) atomicExch(&out.counters[1], 1u);
-        } else if (my_n) {
-            uint32_t mr = mhead;
-            uint32_t k = 0;
-            while (mr != UINT32_MAX && k < my_n) {
-                JoinRowHdr* mh = jrow(match, mr);
-                if (mh->alive &&
-                    jhdr_key_eq(mh, m.key_cols[1 - S], m.KW, kw, nm, false) &&
-                    jpart_cond_ok(m, S, hv, pvb, mh->validbits, jvals(mh))) {
-                    uint32_t orow = my_base + k;
-                    out.ops[orow] = RW_OP_INSERT;
-                    const long long* mv = jvals(mh);
-                    for (int c = 0; c < m.n_out; c++) {
-                        bool from_probe = (int)m.out_src[c] == S;
-                        uint8_t col = m.out_col[c];
-                        int64_t v;
-                        uint8_t valid;
-                        if (from_probe) {
-                            valid = (pvb >> col) & 1;
-                            v = hv[col];
-                        } else {
-                            valid = (mh->validbits >> col) & 1;
-                            v = mv[col];
-                        }
-                        out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-                        out.nulls[(size_t)c * out.cap + orow] = !valid;
-                    }
-                    k++;
-                }
-                mr = mh->next;
-            }
-        }
-        // own-side insert: the record is already in place; link the chain.
-        // Keys are pairwise distinct in the batch, so each touched slot has
-        // exactly one linking thread — plain read-modify-write.
-        if (active) {
-            // record already in place from the scatter kernel (globally
-            // visible across the dispatch boundary); one CAS links it
-            jbucket_insert(own, hash_key(kw, nm, m.KW), row, false);
-        }
-    }
-}
-
-// LDS-window variant of the fused probe+insert phase: with chained
-// buckets and top-bit slot indexing, partition p's OWN slot window
-// [p*cap/P, (p+1)*cap/P) is touched by NO other block during the launch —
-// so the block stages the whole window in LDS, performs the bucket pushes
-// as LDS CASes, and writes the window back sequentially. This converts the
-// insert path's random global CAS traffic (the dominant q8 cost: 290 us of
-// the 540 us monolith step by RW_JOIN_SKIP A/B) into two sequential window
-// copies + LDS atomics. Dynamic LDS = (cap/P)*8 bytes.
-__global__ __launch_bounds__(256) void jpart_probe_insert_lds_kernel(
-    JoinSideDev own, JoinSideDev match, JoinMeta m, int S, JoinOutDev out,
-    const uint32_t* part_base, const uint32_t* row_base,
-    const uint32_t* err) {
-    if (*err) return;
-    // dynamic LDS: [0, wslots) = the block's own slot window;
-    // [wslots, ...) = a per-iteration staging area for blockDim.x records
-    // (a lane-per-record read of 64-B records issues 64 line transactions
-    // per wave per field — staging streams them COALESCED instead)
-    extern __shared__ uint64_t win[];
-    uint32_t rb = *row_base;
-    uint32_t lo = part_base[blockIdx.x];
-    uint32_t hi = part_base[blockIdx.x + 1]; // [JPART_P] holds the total
-    uint32_t n = hi - lo;
-    if (n == 0) return; // window untouched
-    uint32_t wslots = (own.cap_mask + 1) >> JPART_LOG2;
-    uint32_t wbase = blockIdx.x * wslots;
-    uint32_t rwords = own.row_stride >> 3;
-    uint64_t* stage = win + wslots;
-    for (uint32_t i = threadIdx.x; i < wslots; i += blockDim.x)
-        win[i] = own.slots8[wbase + i];
-    int lane = threadIdx.x & 63;
-    uint32_t iters = (n + blockDim.x - 1) / blockDim.x;
-    for (uint32_t it = 0; it < iters; it++) {
-        uint32_t i = it * blockDim.x + threadIdx.x;
-        bool active = i < n;
-        uint32_t row = rb + lo + i;
-        // cooperative coalesced staging of this iteration's records
-        {
-            uint32_t first = lo + it * blockDim.x;
-            uint32_t count = n - it * blockDim.x;
-            if (count > blockDim.x) count = blockDim.x;
-            const uint64_t* src =
-                (const uint64_t*)(own.rows +
-                                  (size_t)(rb + first) * own.row_stride);
-            uint32_t words = count * rwords;
-            __syncthreads();
-            for (uint32_t w = threadIdx.x; w < words; w += blockDim.x)
-                stage[w] = src[w];
-            __syncthreads();
-        }
-        int64_t kw[MAX_KW];
-        uint32_t nm = 0;
-        JoinRowHdr* hd = nullptr;   // GLOBAL record (next-link target)
-        long long* hv = nullptr;    // LDS copy (reads)
-        uint32_t pvb = 0;
-        uint64_t h64 = 0;
-        if (active) {
-            hd = jrow(own, row);
-            JoinRowHdr* lh = (JoinRowHdr*)(stage + (size_t)threadIdx.x * rwords);
-            hv = (long long*)((uint8_t*)lh + 16);
-            pvb = lh->validbits;
-            for (int k = 0; k < m.KW; k++) {
-                uint8_t col = m.key_cols[S][k];
-                bool valid = (pvb >> col) & 1;
-                kw[k] = valid ? hv[col] : 0;
-                nm |= (uint32_t)(!valid) << k;
-            }
-            h64 = hash_key(kw, nm, m.KW);
-        }
-        // probe the match side (immutable during this launch)
-        uint32_t mhead = UINT32_MAX;
-        uint32_t my_n = 0;
-        if (active) {
-            mhead = jbucket_head(match, h64, false);
-            uint32_t mr = mhead;
-            while (mr != UINT32_MAX) {
-                JoinRowHdr* mh = jrow(match, mr);
-                if (mh->alive &&
-                    jhdr_key_eq(mh, m.key_cols[1 - S], m.KW, kw, nm, false) &&
-                    jpart_cond_ok(m, S, hv, pvb, mh->validbits, jvals(mh)))
-                    my_n++;
-                mr = mh->next;
-            }
-        }
-        // ballot fast path for my_n<=1 (see join_probe_kernel)
-        uint64_t multi = __ballot(my_n > 1);
-        uint32_t total, my_base;
-        uint32_t base = 0;
-        if (!multi) {
-            uint64_t got = __ballot(my_n != 0);
-            total = (uint32_t)__popcll(got);
-            if (lane == 0 && total) base = atomicAdd(&out.counters[0], total);
-            base = (uint32_t)__shfl((int)base, 0);
-            my_base = base + (uint32_t)__popcll(got & ((1ULL << lane) - 1));
-        } else {
-            uint32_t incl = my_n;
-            for (int d = 1; d < 64; d <<= 1) {
-                uint32_t o = __shfl_up(incl, d);
-                if (lane >= d) incl += o;
-            }
-            total = (uint32_t)__shfl((int)incl, 63);
-            if (lane == 0 && total) base = atomicAdd(&out.counters[0], total);
-            base = (uint32_t)__shfl((int)base, 0);
-            my_base = base + incl - my_n;
-        }
-        if (total && base + total > out.cap) {
-            if (lane == 0) atomicExch(&out.counters[1], 1u);
-        } else if (my_n) {
-            uint32_t mr = mhead;
-            uint32_t k = 0;
-            while (mr != UINT32_MAX && k < my_n) {
-                JoinRowHdr* mh = jrow(match, mr);
-                if (mh->alive &&
-                    jhdr_key_eq(mh, m.key_cols[1 - S], m.KW, kw, nm, false) &&
-                    jpart_cond_ok(m, S, hv, pvb, mh->validbits, jvals(mh))) {
-                    uint32_t orow = my_base + k;
-                    out.ops[orow] = RW_OP_INSERT;
-                    const long long* mv = jvals(mh);
-                    for (int c = 0; c < m.n_out; c++) {
-                        bool from_probe = (int)m.out_src[c] == S;
-                        uint8_t col = m.out_col[c];
-                        int64_t v;
-                        uint8_t valid;
-                        if (from_probe) {
-                            valid = (pvb >> col) & 1;
-                            v = hv[col];
-                        } else {
-                            valid = (mh->validbits >> col) & 1;
-                            v = mv[col];
-                        }
-                        out.vals[(size_t)c * out.cap + orow] = valid ? v : 0;
-                        out.nulls[(size_t)c * out.cap + orow] = !valid;
-                    }
-                    k++;
-                }
-                mr = mh->next;
-            }
-        }
-        // own-side bucket push in LDS (visibility via the window writeback
-        // + the inter-dispatch flush; no drains needed — nothing walks the
-        // own side within an all-Insert launch)
-        if (active) {
-            uint32_t local = jslot_start(h64, own.cap_mask) - wbase;
-            uint64_t old = win[local];
-            for (;;) {
-                hd->next = (uint32_t)old ? jhead_of(old) : UINT32_MAX;
-                uint64_t want =
-                    ((uint64_t)row << 32) | ((uint32_t)old | jbloom_bit(h64));
-                uint64_t prev = atomicCAS((unsigned long long*)&win[local],
-                                          old, want);
-                if (prev == old) break;
-                old = prev;
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < wslots; i += blockDim.x)
-        own.slots8[wbase + i] = win[i];
 }
 
 // join state restore: append decoded state rows + bucket links + degrees
@@ -7275,47 +6662,6 @@ struct HashJoin {
     uint32_t last_sparse_rows = 0;
     bool sparse_out = false;
 
-    // partitioned-pipeline device buffers (lazily allocated; ~260 KB)
-    uint32_t* d_ptot = nullptr;  // padded per-partition totals (count)
-    uint32_t* d_pcur = nullptr;  // padded per-partition scatter cursors
-    uint32_t* d_part_base = nullptr;
-    uint32_t* d_row_base = nullptr;
-
-    // The partitioned pipeline handles the shape under which the
-    // batch-parallel insert commutes with the reference's sequential loop:
-    // inner join, every visible row an Insert (same-side rows never match
-    // each other, so equal keys within the batch are independent),
-    // whole-batch range.
-    bool can_partition(const JoinBatchDev& b, uint32_t r0, uint32_t r1) {
-        // Default OFF: with LIC-resident bloom-bucket slots the fused
-        // monolithic kernel beat the 4-phase pipeline on q8 (0.50 vs
-        // 0.61 ms/1M rows — the prelude's ~125 us exceeds the probe
-        // phase's locality win; profiles/r02 series). Kept selectable
-        // (RW_JOIN_PART=1) and parity-covered.
-        const char* e = getenv("RW_JOIN_PART");
-        if (!e || atoi(e) == 0) return false;
-        if (m.join_type != RW_JOIN_INNER || m.append_only) return false;
-        if (!b.all_insert || b.vis) return false;
-        if (r0 != 0 || r1 != b.n_rows) return false;
-        if (b.n_rows < JPART_MIN_ROWS) return false;
-        // partitions must map to multi-slot windows on both sides
-        if (side[0].cap_mask < 4 * JPART_P - 1 ||
-            side[1].cap_mask < 4 * JPART_P - 1)
-            return false;
-        return true;
-    }
-
-    int ensure_part_bufs() {
-        if (d_ptot) return RW_OK;
-        HIP_TRY(hipMalloc(&d_ptot, (size_t)JPART_P * JPART_PAD * 4));
-        HIP_TRY(hipMemsetAsync(d_ptot, 0, (size_t)JPART_P * JPART_PAD * 4,
-                               stream));
-        HIP_TRY(hipMalloc(&d_pcur, (size_t)JPART_P * JPART_PAD * 4));
-        HIP_TRY(hipMalloc(&d_part_base, (size_t)(JPART_P + 1) * 4));
-        HIP_TRY(hipMalloc(&d_row_base, 4));
-        return RW_OK;
-    }
-
     int probe(int s, const JoinBatchDev& b, bool timed, uint32_t r0, uint32_t r1) {
         uint32_t blocks = (r1 - r0 + 255) / 256;
         // one row per lane up to 16K blocks: a grid-stride iteration
@@ -7334,10 +6680,7 @@ struct HashJoin {
             if (ev_harvest(slot) != RW_OK) return RW_E_INTERNAL;
             HIP_TRY(hipEventRecord(ev0[slot], stream));
         }
-        const char* dbg_e = getenv("RW_JOIN_SKIP"); // bench A/B only:
-        int dbg_skip = dbg_e ? atoi(dbg_e) : 0; // 1=no emits, 2=no own insert
-        if (m.join_type == RW_JOIN_INNER && !m.append_only &&
-            !can_partition(b, r0, r1) && r0 == 0) {
+        if (m.join_type == RW_JOIN_INNER && !m.append_only && r0 == 0) {
             // pre-assigned sparse output + one-bump record reservation
             if (!d_probe_base) {
                 HIP_TRY(hipMalloc(&d_probe_base, 4));
@@ -7352,34 +6695,12 @@ struct HashJoin {
             last_sparse_rows = b.n_rows;
             sparse_out = true;
         }
-        if (can_partition(b, r0, r1)) {
-            int rc = ensure_part_bufs();
-            if (rc != RW_OK) return rc;
-            jpart_count_kernel<<<256, 1024, 0, stream>>>(b, m, s, d_ptot);
-            jpart_scan_kernel<<<1, 1024, 0, stream>>>(
-                d_ptot, d_pcur, d_part_base, side[s].row_cursor,
-                side[s].row_cap, d_row_base, out.counters + 1);
-            jpart_scatter_kernel<<<2048, 256, 0, stream>>>(
-                b, m, s, side[s], d_pcur, d_row_base, out.counters + 1);
-            uint32_t wslots = (side[s].cap_mask + 1) >> JPART_LOG2;
-            size_t shmem = (size_t)wslots * 8 + 256 * side[s].row_stride;
-            if (shmem <= 64 * 1024) {
-                jpart_probe_insert_lds_kernel<<<JPART_P, 256, shmem,
-                                                stream>>>(
-                    side[s], side[1 - s], m, s, out, d_part_base, d_row_base,
-                    out.counters + 1);
-            } else {
-                jpart_probe_insert_kernel<<<JPART_P, 256, 0, stream>>>(
-                    side[s], side[1 - s], m, s, out, d_part_base, d_row_base,
-                    out.counters + 1);
-            }
-        } else if (m.join_type != RW_JOIN_INNER) {
+        if (m.join_type != RW_JOIN_INNER) {
             join_probe_noninner_kernel<<<blocks, 256, 0, stream>>>(
-                b, side[s], side[1 - s], m, s, out, r0, r1, dbg_skip);
+                b, side[s], side[1 - s], m, s, out, r0, r1);
         } else {
             join_probe_kernel<<<blocks, 256, 0, stream>>>(
-                b, side[s], side[1 - s], m, s, out, r0, r1, d_probe_base,
-                dbg_skip);
+                b, side[s], side[1 - s], m, s, out, r0, r1, d_probe_base);
         }
         if (timed) {
             HIP_TRY(hipEventRecord(ev1[slot], stream));
@@ -8039,12 +7360,6 @@ struct HashJoin {
                 hipEventDestroy(ev0[s]);
                 hipEventDestroy(ev1[s]);
             }
-        if (d_ptot) {
-            hipFree(d_ptot);
-            hipFree(d_pcur);
-            hipFree(d_part_base);
-            hipFree(d_row_base);
-        }
         if (d_probe_base) {
             hipFree(d_probe_base);
             hipFree(d_emit_count);
@@ -10058,217 +9373,6 @@ __global__ void membw_rand_probe_kernel(const unsigned long long* __restrict__ p
         acc += p[(h % n_lines) * 8]; // 64-B line stride (8 u64)
     }
     if (acc == 0xdeadbeefdeadbeefULL) *sink = acc;
-}
-
-// q8-SHAPE ladder: a stripped reproduction of the inner probe kernel's
-// per-row structure with stages toggled by `mode` bits, against synthetic
-// tables of the bench's sizes — pinpoints which stage carries the gap
-// between the ~30 us/1M-row random-access ceiling and the ~490 us kernel.
-// mode bits: 1 = wave-scan output reservation, 2 = emit writes (8 cols,
-// columnar), 4 = own-side insert (slot CAS + 64-B record write + link).
-__global__ void q8shape_kernel(const int64_t* __restrict__ k0,
-                               const int64_t* __restrict__ k1,
-                               const int64_t* __restrict__ k2,
-                               const uint64_t* __restrict__ mslots,
-                               uint32_t mcap_mask,
-                               const uint64_t* __restrict__ mrows,
-                               uint32_t mrow_mask, uint64_t* oslots,
-                               uint32_t ocap_mask, uint64_t* orows,
-                               uint32_t* ocursor, int64_t* out_vals,
-                               uint8_t* out_ops, uint32_t out_cap,
-                               uint32_t n, int mode, uint32_t* sink) {
-    uint32_t stride = gridDim.x * blockDim.x;
-    uint32_t iters = (n + stride - 1) / stride;
-    int lane = threadIdx.x & 63;
-    for (uint32_t it = 0; it < iters; it++) {
-        uint32_t r = it * stride + blockIdx.x * blockDim.x + threadIdx.x;
-        bool active = r < n;
-        int64_t kw[3] = {0, 0, 0};
-        uint64_t h = 0x20210401u;
-        if (active) {
-            kw[0] = k0[r];
-            kw[1] = k1[r];
-            kw[2] = k2[r];
-            for (int i = 0; i < 3; i++) h = mix64(h ^ (uint64_t)kw[i]);
-        }
-        if (mode & 16) { // byte streams like the real kernel (ops + valid)
-            if (active) {
-                h ^= out_ops[r & (out_cap - 1)]; // stand-in ops stream read
-                for (int i = 0; i < 3; i++)
-                    h += ((const uint8_t*)k0)[r]; // validity-byte stand-ins
-            }
-        }
-        uint32_t my_n = 0;
-        uint64_t mv0 = 0;
-        if (active) {
-            uint32_t slot = (uint32_t)(h >> (64 - __popc(mcap_mask)));
-            uint64_t packed = mslots[slot];
-            if ((uint32_t)packed & (1u << ((uint32_t)(h >> 32) & 31))) {
-                uint32_t head = (uint32_t)(packed >> 32) & mrow_mask;
-                if (mode & 8) {
-                    // the real kernel's walk SHAPE: header fields, per-key
-                    // branchy compares, next chase with alive checks
-                    uint32_t row2 = head;
-                    int guard = 0;
-                    while (row2 != UINT32_MAX && guard++ < 4) {
-                        const uint64_t* rec = mrows + (size_t)row2 * 8;
-                        uint64_t hdr = rec[0]; // alive | next
-                        uint64_t vb = rec[1];
-                        bool eq = true;
-                        for (int i = 0; i < 3 && eq; i++)
-                            eq = ((int64_t)rec[2 + i] ^ kw[i]) != 1; // ~always true
-                        if ((hdr & 1) && eq && (vb | 1)) {
-                            my_n++;
-                            mv0 += rec[5];
-                        }
-                        // synthetic records have garbage next: terminate
-                        row2 = UINT32_MAX;
-                    }
-                } else {
-                    // one 64-B record line: read all 8 words
-                    const uint64_t* rec = mrows + (size_t)head * 8;
-                    uint64_t acc = 0;
-                    for (int w = 0; w < 8; w++) acc += rec[w];
-                    mv0 = acc;
-                    my_n = 1;
-                }
-            }
-        }
-        uint32_t my_base = 0;
-        if (mode & 1) {
-            uint32_t incl = my_n;
-            for (int d = 1; d < 64; d <<= 1) {
-                uint32_t o = __shfl_up(incl, d);
-                if (lane >= d) incl += o;
-            }
-            uint32_t total = (uint32_t)__shfl((int)incl, 63);
-            uint32_t base = 0;
-            if (lane == 0 && total) base = atomicAdd(ocursor, total);
-            base = (uint32_t)__shfl((int)base, 0);
-            my_base = base + incl - my_n;
-        }
-        if (mode & 64) { // ballot-form reservation (1 ballot + popcounts)
-            uint64_t got = __ballot(my_n != 0);
-            uint32_t total = (uint32_t)__popcll(got);
-            uint32_t base = 0;
-            if (lane == 0 && total) base = atomicAdd(ocursor, total);
-            base = (uint32_t)__shfl((int)base, 0);
-            my_base = base + (uint32_t)__popcll(got & ((1ULL << lane) - 1));
-        }
-        if (mode & 128) { // pre-assigned output slot: NO cross-lane ops
-            my_base = r;
-        }
-        if ((mode & 2) && my_n) {
-            uint32_t orow = my_base & (out_cap - 1);
-            out_ops[orow] = 0;
-            for (int c = 0; c < 8; c++)
-                out_vals[(size_t)c * out_cap + orow] =
-                    (int64_t)(mv0 + kw[c % 3]);
-        }
-        if ((mode & 4) && active) {
-            uint32_t oslot = (uint32_t)(h >> (64 - __popc(ocap_mask)));
-            // record append at a wave-aggregated cursor position
-            uint64_t wmask = __ballot(true);
-            int leader = 63 - __clzll(wmask);
-            uint32_t base2 = 0;
-            if (lane == leader)
-                base2 = atomicAdd(ocursor + 16, (uint32_t)__popcll(wmask));
-            base2 = (uint32_t)__shfl((int)base2, leader);
-            uint32_t row =
-                (base2 + (uint32_t)__popcll(wmask & ((1ULL << lane) - 1))) &
-                mrow_mask;
-            uint64_t* rec = orows + (size_t)row * 8;
-            for (int w = 0; w < 8; w++) rec[w] = h + w;
-            // bucket push: CAS on the slot
-            uint64_t old = __hip_atomic_load(&oslots[oslot], RLX);
-            for (;;) {
-                rec[1] = (uint32_t)old ? (old >> 32) : 0xFFFFFFFFull;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                uint64_t want = ((uint64_t)row << 32) |
-                                ((uint32_t)old | (1u << ((uint32_t)(h >> 32) & 31)));
-                uint64_t prev = atomicCAS((unsigned long long*)&oslots[oslot],
-                                          old, want);
-                if (prev == old) break;
-                old = prev;
-            }
-        }
-        if (active && mv0 == 0xdeadbeefdeadbeefULL) *sink = 1;
-    }
-}
-
-__global__ void q8shape_slot_fill_kernel(uint64_t* slots, uint32_t cap,
-                                         uint32_t rmask) {
-    uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t s2 = blockIdx.x * blockDim.x + threadIdx.x; s2 < cap;
-         s2 += stride)
-        slots[s2] = ((uint64_t)(mix64(s2) & rmask) << 32) | 0xFFFFFFFFull;
-}
-
-__global__ void q8shape_fill_kernel(int64_t* k0, int64_t* k1, int64_t* k2,
-                                    uint32_t n) {
-    uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < n;
-         r += stride) {
-        k0[r] = (int64_t)mix64(r * 2654435761u + 1);
-        k1[r] = (int64_t)mix64(r * 40503u + 2);
-        k2[r] = (int64_t)mix64(r * 2246822519u + 3);
-    }
-}
-
-extern "C" int rw_q8shape_probe(uint32_t n_rows, int mode, double* us_out) {
-    // bench-sized synthetic state: 2^24-slot tables (134 MB), 16M-row
-    // record stores (1 GiB), q8-like 50%-hit blooms
-    uint32_t mcap = 1u << 24, rmask = (1u << 24) - 1;
-    size_t rbytes = (size_t)(rmask + 1) * 64;
-    int64_t *k0, *k1, *k2;
-    uint64_t *mslots, *mrows, *oslots, *orows;
-    uint32_t* ocursor;
-    int64_t* out_vals;
-    uint8_t* out_ops;
-    uint32_t out_cap = 1u << 22;
-    if (hipMalloc(&k0, (size_t)n_rows * 8) != hipSuccess) return RW_E_INTERNAL;
-    (void)hipMalloc(&k1, (size_t)n_rows * 8);
-    (void)hipMalloc(&k2, (size_t)n_rows * 8);
-    (void)hipMalloc(&mslots, (size_t)mcap * 8);
-    (void)hipMalloc(&mrows, rbytes);
-    (void)hipMalloc(&oslots, (size_t)mcap * 8);
-    (void)hipMalloc(&orows, rbytes);
-    (void)hipMalloc(&ocursor, 256);
-    (void)hipMalloc(&out_vals, (size_t)8 * out_cap * 8);
-    (void)hipMalloc(&out_ops, out_cap);
-    q8shape_fill_kernel<<<2048, 256>>>(k0, k1, k2, n_rows);
-    q8shape_slot_fill_kernel<<<2048, 256>>>(mslots, mcap, rmask);
-    (void)hipMemset(mrows, 1, rbytes);
-    (void)hipMemset(oslots, 0, (size_t)mcap * 8);
-    (void)hipMemset(ocursor, 0, 256);
-    uint32_t* sink;
-    (void)hipMalloc(&sink, 4);
-    uint32_t blocks = (n_rows + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    q8shape_kernel<<<blocks, 256>>>(k0, k1, k2, mslots, mcap - 1, mrows,
-                                    rmask, oslots, mcap - 1, orows, ocursor,
-                                    out_vals, out_ops, out_cap, n_rows, mode,
-                                    sink);
-    (void)hipEventRecord(e0);
-    for (int i = 0; i < 8; i++)
-        q8shape_kernel<<<blocks, 256>>>(k0, k1, k2, mslots, mcap - 1, mrows,
-                                        rmask, oslots, mcap - 1, orows,
-                                        ocursor, out_vals, out_ops, out_cap,
-                                        n_rows, mode, sink);
-    (void)hipEventRecord(e1);
-    if (hipEventSynchronize(e1) != hipSuccess) return RW_E_INTERNAL;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *us_out = ms * 1000.0 / 8;
-    hipFree(k0); hipFree(k1); hipFree(k2); hipFree(mslots); hipFree(mrows);
-    hipFree(oslots); hipFree(orows); hipFree(ocursor); hipFree(out_vals);
-    hipFree(out_ops); hipFree(sink);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return RW_OK;
 }
 
 // random atomicAdd throughput (the insert path's slot-CAS analogue)

@@ -1151,22 +1151,18 @@ def test_topn_checkpoint_spill_parity():
     o.close()
 
 
-def test_join_partitioned_pipeline_parity():
-    # The hash-prefix-partitioned probe/insert pipeline (jpart_* kernels)
-    # engages only for all-Insert unique-key inner batches of >= 131072
-    # rows (rw_amd.hip can_partition). Drive it with q8-shaped batches on
-    # BOTH sides — so partitioned inserts build the chains that later
-    # partitioned probes walk — and compare output multisets AND the
-    # checkpoint spill bytes (which read back the scattered row records)
+def test_join_large_insert_batches_parity():
+    # All-Insert unique-key inner batches of 140 000 rows, q8-shaped, on
+    # BOTH sides — so one launch's inserts build the chains that later
+    # launches' probes walk across many blocks — comparing output multisets
+    # AND the checkpoint spill bytes (which read back the row records)
     # against the oracle.
-    import os
-    os.environ["RW_JOIN_PART"] = "1"  # opt into the partitioned pipeline
     rng = np.random.default_rng(77)
     t4 = [T_I64, T_TS, T_TS, T_I64]
     kw = dict(key_l=[0, 1, 2], key_r=[0, 1, 2], pk_l=[3], pk_r=[3])
     g = ffi.HashJoin(gpu(), JOIN_INNER, t4, t4, **kw)
     o = ffi.HashJoin(oracle(), JOIN_INNER, t4, t4, **kw)
-    N = 140_000  # > JPART_MIN_ROWS
+    N = 140_000
     rowid = 0
 
     def batch(ids, null_every=0):
@@ -1179,14 +1175,13 @@ def test_join_partitioned_pipeline_parity():
         valid = np.ones(n, np.uint8)
         if null_every:
             # null join keys (never-match under non-null-safe): distinct
-            # (ws, we) keeps the batch's keys pairwise distinct so the
-            # partitioned path still engages
+            # (ws, we) keeps the batch's keys pairwise distinct
             valid[::null_every] = 0
         return ffi.Chunk(t4, np.zeros(n, np.uint8), [ids, ws, we, rid],
                          [valid, np.ones(n, np.uint8), np.ones(n, np.uint8),
                           np.ones(n, np.uint8)])
 
-    # build side: two partitioned insert batches (distinct ids, no matches)
+    # build side: two insert batches (distinct ids, no matches)
     perm = rng.permutation(400_000).astype(np.int64)
     pushes = [
         (SIDE_RIGHT, batch(perm[:N])),
@@ -1212,7 +1207,6 @@ def test_join_partitioned_pipeline_parity():
         assert sg == so, (f"side {side}: spill {len(sg)} vs {len(so)} bytes")
     g.close()
     o.close()
-    del os.environ["RW_JOIN_PART"]
 
 
 def test_q7_pipeline_parity():
@@ -1372,6 +1366,93 @@ def test_join_inner_multimatch_sparse_overflow():
     assert mg == mo and len(mg) > 30_000, f"{len(mg)} vs {len(mo)}"
     g.close()
     o.close()
+
+
+def test_join_inner_wide_records():
+    # 7-column build side: record stride 16 + 56 = 72 -> 96 B, past the
+    # register-resident walk's 64-B limit, so the probe takes the
+    # field-by-field walk, the matched_row single-match emit and (on
+    # repeated keys) the multi-match second walk into the overflow region.
+    # Batches of 300 rows: more than four waves, not a multiple of 64.
+    tl = [T_I64, T_I64]
+    tr = [T_I64] * 7
+    kw = dict(key_l=[0], key_r=[0], pk_l=[1], pk_r=[1])
+    g = ffi.HashJoin(gpu(), JOIN_INNER, tl, tr, **kw)
+    o = ffi.HashJoin(oracle(), JOIN_INNER, tl, tr, **kw)
+    n = 300
+
+    def right(keys, pk0, op=ffi.OP_INSERT):
+        pk = np.arange(pk0, pk0 + len(keys))
+        cols = [keys, pk] + [pk * 10 + c for c in range(2, 7)]
+        valids = [np.ones(len(keys), np.uint8) for _ in tr]
+        valids[4] = (pk % 3 != 0).astype(np.uint8)  # NULL payload cells
+        return ffi.Chunk(tr, np.full(len(keys), op, np.uint8), cols, valids)
+
+    def left(keys, pk0, op=ffi.OP_INSERT):
+        pk = np.arange(pk0, pk0 + len(keys))
+        return mk_chunk(tl, np.full(len(keys), op, np.uint8), [keys, pk])
+
+    uniq = np.arange(n, dtype=np.int64)
+    rep = np.repeat(np.arange(1000, 1050, dtype=np.int64), 3)
+    fill = np.arange(2000, 2000 + n - len(rep), dtype=np.int64)
+    l1 = np.concatenate([uniq[::2], np.arange(5000, 5000 + n // 2)])
+    l2 = np.concatenate([np.arange(1000, 1050),
+                         np.arange(6000, 6000 + n - 50)]).astype(np.int64)
+    pushes = [
+        (SIDE_RIGHT, right(uniq, 0)),
+        # half hit one build row each: single-match matched_row emit
+        (SIDE_LEFT, left(l1, 100_000)),
+        (SIDE_RIGHT, right(np.concatenate([rep, fill]), n)),
+        # 50 keys with three build rows each: second walk + overflow rows
+        (SIDE_LEFT, left(l2, 200_000)),
+        (SIDE_LEFT, left(l1[:100], 100_000, ffi.OP_DELETE)),
+        (SIDE_RIGHT, right(uniq[150:250], 150, ffi.OP_DELETE)),
+    ]
+    for i, (side, c) in enumerate(pushes):
+        g.push(side, c)
+        o.push(side, c)
+        mg = rows_multiset(g.poll_all())
+        mo = rows_multiset(o.poll_all())
+        assert mg == mo, f"push {i}: GPU {len(mg)} rows vs oracle {len(mo)}"
+        assert len(mo) == [0, 150, 0, 150, 100, 25][i], f"push {i}: {len(mo)}"
+    for side in (SIDE_LEFT, SIDE_RIGHT):
+        sg = ffi.join_checkpoint_drain(gpu(), g.h, side)
+        so = ffi.join_checkpoint_drain(ffi.oracle(), o.h, side)
+        assert sg == so, f"side {side}: spill {len(sg)} vs {len(so)} bytes"
+    g.close()
+    o.close()
+
+
+def test_join_inner_append_only_gpu():
+    # the append-only inner path (own emit loop, plain stores, matched row
+    # retired on emit): the reference's golden chunks
+    # (test_oracle_join.py::test_inner_join_append_only), then two 300-row
+    # insert-only batches per side, keys unique within a side and about
+    # half shared across sides
+    t3 = [T_I64, T_I64, T_I64]
+    kw = dict(key_l=[0, 1], key_r=[0, 1], pk_l=[], pk_r=[],
+              null_safe=[0, 0], append_only=True)
+    g = ffi.HashJoin(gpu(), JOIN_INNER, t3, t3, **kw)
+    o = ffi.HashJoin(oracle(), JOIN_INNER, t3, t3, **kw)
+
+    def batch(k0, base):
+        n = len(k0)
+        return mk_chunk(t3, np.zeros(n, np.uint8),
+                        [k0, k0 * 2 + 1, np.arange(base, base + n)])
+
+    a = np.arange(100, 700, dtype=np.int64)      # left keys
+    b = np.arange(400, 1000, dtype=np.int64)     # right keys: 300 shared
+    pushes = [
+        (SIDE_LEFT, from_pretty(" I I I\n + 1 4 1\n + 2 5 2\n + 3 6 3")),
+        (SIDE_LEFT, from_pretty(" I I I\n + 4 9 4\n + 5 10 5")),
+        (SIDE_RIGHT, from_pretty(" I I I\n + 2 5 1\n + 4 9 2\n + 6 9 3")),
+        (SIDE_RIGHT, from_pretty(" I I I\n + 1 4 4\n + 3 6 5")),
+        (SIDE_LEFT, batch(a[::2], 10_000)),
+        (SIDE_RIGHT, batch(b[::2], 20_000)),
+        (SIDE_LEFT, batch(a[1::2], 30_000)),
+        (SIDE_RIGHT, batch(b[1::2], 40_000)),
+    ]
+    run_join_and_compare(g, o, pushes)
 
 
 def test_join_epoch_ingest_mode_parity():
