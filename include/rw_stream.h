@@ -415,6 +415,26 @@ int rw_agg_dedup_restore(void* h, int di, const uint8_t* buf, uint64_t len);
 int rw_join_degree_drain(void* h, int side, uint8_t** buf, uint64_t* len);
 void rw_spill_free(uint8_t* buf);
 
+/* One epoch of the device-resident path, fully asynchronous: apply rows
+ * [r0, r1) of a batch preloaded with rw_agg_bench_preload, then the
+ * stream-ordered checkpoint flush. The executor is left exactly as the
+ * separate apply and rw_agg_flush_launch leave it. With RW_AGG_FUSE_FLUSH=1
+ * in the environment when the executor is created, and where the launch
+ * takes the dense span kernel, the executor keeps plain value states and
+ * the dirty counts seen at earlier syncs were small, the flush runs inside
+ * the apply launch; that measured slower than two launches on the MI355X
+ * and is off by default. */
+int rw_agg_apply_flush_launch(void* h, void* batch, uint32_t r0, uint32_t r1,
+                              uint64_t epoch);
+/* Debug: 0 = the dirty-count policy, 1 = fuse wherever the launch is
+ * eligible, 2 = never. rw_agg_debug_fuse_allowed reports what the current mode
+ * decides now for an eligible launch (1 = fuse). */
+int rw_agg_debug_set_fuse(void* h, int mode);
+int rw_agg_debug_fuse_allowed(void* h);
+/* Launches that carried the flush so far; the policy's dirty-count limit. */
+long long rw_agg_debug_fused_launches(void* h);
+uint32_t rw_agg_debug_fuse_max(void);
+
 #ifdef __cplusplus
 }
 #endif

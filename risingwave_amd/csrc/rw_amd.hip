@@ -260,6 +260,11 @@ __device__ __forceinline__ void st_i64(int64_t* p, int64_t v) {
     __hip_atomic_store((unsigned long long*)p, (unsigned long long)v, RLX);
 }
 
+// AggTableDev::counters: words, and the fused apply's arrival-ticket shards
+#define AGG_FUSE_SHARDS 64u
+#define AGG_CTR_SHARD0 32u
+#define AGG_CTR_WORDS (AGG_CTR_SHARD0 + 32u * AGG_FUSE_SHARDS)
+
 // Find-or-insert into an open-addressed key table (linear probe).
 // key_nulls is a u32-per-slot null mask. Returns slot, or -1 on table-full.
 __device__ __forceinline__ uint32_t table_find_or_insert(
@@ -712,7 +717,10 @@ struct AggTableDev {
     uint8_t* has_prev;  // [cap]
     uint32_t* dirty_flag;
     uint32_t* dirty_list;
-    uint32_t* counters; // [0]=dirty_count [1]=out_cursor [2]=overflow flag
+    // [0]=dirty_count [1]=out_cursor [2]=overflow flag [3]=flush-kernel ticket
+    // [4]=fused-apply arrival ticket [5]=largest dirty count a flush has seen
+    // [AGG_CTR_SHARD0 + 32 s]=arrival ticket of shard s, one 128-B line each
+    uint32_t* counters;
                         // [3]=flush arrival ticket (0 outside a flush)
     // flush output buffers (records of width gk+calls)
     long long* out_vals;
@@ -1146,7 +1154,12 @@ __device__ __forceinline__ void dense_load(const AggBatch& b,
 // non-uniform tile then takes the segmented-scan path unchanged. All
 // combiners are commutative and associative on i64 (wrapping add
 // included), so the table state after the launch is bit-identical.
-template <int n_calls, int CS = -1, bool SPAN = false>
+//
+// PUBLISH (the fused-flush span kernel only, see its tail): `commit`'s two
+// plain stores, the dirty_list entry and the has byte, become write-through
+// agent-scope stores, so that the launch's last-arriving block can read them
+// behind one acquire with no release fence in any producer.
+template <int n_calls, int CS = -1, bool SPAN = false, bool PUBLISH = false>
 __device__ __forceinline__ void agg_apply_dense4_body(
         const AggBatch& b, const AggTableDev& t, AggCallDev c0, AggCallDev c1,
         AggCallDev c2, AggCallDev c3, uint32_t r0, uint32_t r1,
@@ -1183,10 +1196,16 @@ __device__ __forceinline__ void agg_apply_dense4_body(
             if (ld_u32(&t.dirty_flag[slot]) == 0 &&
                 atomicCAS(&t.dirty_flag[slot], 0u, 1u) == 0u) {
                 uint32_t i = atomicAdd(&t.counters[0], 1u);
-                t.dirty_list[i] = slot;
+                if (PUBLISH) st_u32(&t.dirty_list[i], slot);
+                else t.dirty_list[i] = slot;
             }
             memo_dirtied = true;
         }
+        auto set_has = [&](uint8_t* has) {
+            if (has[slot]) return;
+            if (PUBLISH) __hip_atomic_store(&has[slot], (uint8_t)1, RLX);
+            else has[slot] = 1;
+        };
         _Pragma("unroll") for (int ci = 0; ci < n_calls; ci++) {
             long long* acc = t.acc + (size_t)ci * cap;
             uint8_t* has = t.has + (size_t)ci * cap;
@@ -1197,16 +1216,16 @@ __device__ __forceinline__ void agg_apply_dense4_body(
             switch (calls[ci].kind) {
                 case RW_AGG_MIN:
                     atomic_min_i64(&acc[slot], vals[ci]);
-                    if (!has[slot]) has[slot] = 1;
+                    set_has(has);
                     break;
                 case RW_AGG_MAX:
                     atomic_max_i64(&acc[slot], vals[ci]);
-                    if (!has[slot]) has[slot] = 1;
+                    set_has(has);
                     break;
                 case RW_AGG_SUM:
                 case RW_AGG_SUM0:
                     atomic_add_i64(&acc[slot], vals[ci]);
-                    if (!has[slot]) has[slot] = 1;
+                    set_has(has);
                     break;
                 default:
                     atomic_add_i64(&acc[slot], vals[ci]);
@@ -1463,12 +1482,125 @@ __global__ __launch_bounds__(256, 8) void agg_apply_dense4_kernel_w8(
 
 // The same with the run-carrying span mapping (see agg_apply_dense4_body):
 // the launch gives each wave `span_tiles` adjacent tiles.
-template <int n_calls, int CS>
+//
+// FUSE: the launch also runs the epoch's checkpoint flush, so an epoch step
+// is one launch and one boundary. `fuse_arg` packs the call
+// kinds (one per byte, bits 0-15) and row_count_index (bits 16-23); FUSE =
+// false ignores it and is the kernel as it was.
+//  - publish: `commit` stores the dirty_list entry and the has byte
+//    write-through (PUBLISH above); the table words and the accumulators
+//    are agent-scope atomics already. No fence in any producer.
+//  - arrival: every wave drains its memory operations, the block meets at a
+//    barrier, thread 0 draws a ticket (relaxed, agent scope) on its shard
+//    word, the shard's last arriver one on counters[4].
+//  - the block drawing the last top ticket is the flusher: thread 0 takes one
+//    agent acquire and waits for it, the block learns "last" through one
+//    LDS word behind the barrier, then runs agg_flush_fast_pass over every
+//    dirty slot with stride 256 (right for any count, only slow for a large
+//    one: HashAgg::fuse_allowed keeps those on the flush kernel).
+//  - reset: the flusher zeroes counters[0], [1] and the ticket behind its
+//    last pass; counters[2] stays sticky.
+// Nothing waits on another block, and no step depends on where blocks run.
+template <int KW, int NC, bool PRELOADED = false>
+__device__ __forceinline__ void agg_flush_fast_pass(
+        const AggTableDev& t, int row_count_index, uint32_t kinds, size_t cap,
+        int lane, uint32_t i, uint32_t n_dirty, uint32_t slot = 0);
+
+// The tail reads the table descriptor from the kernel-argument segment
+// again (scalar loads) instead of keeping its ~30 further pointer SGPRs live
+// across the main loop, whose register allocation it must leave alone. The
+// descriptor is the kernel's second argument, behind the AggBatch.
+__device__ __forceinline__ AggTableDev span_tail_table() {
+    constexpr size_t off = (sizeof(AggBatch) + alignof(AggTableDev) - 1) /
+                           alignof(AggTableDev) * alignof(AggTableDev);
+    using kptr = const __attribute__((address_space(4))) char*;
+    uint64_t a = (uint64_t)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + off);
+    asm volatile("" : "+s"(a)); // not the main loop's copy of the same bytes
+    // the asm's result counts as divergent; back to scalar registers
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+    auto* p = (const __attribute__((address_space(4))) AggTableDev*)(
+        ((uint64_t)hi << 32) | lo);
+    AggTableDev tt;
+    __builtin_memcpy(&tt, p, sizeof(tt));
+    return tt;
+}
+
+template <int n_calls, int CS, bool FUSE = false>
 __global__ __launch_bounds__(256, 8) void agg_apply_dense4_kernel_span(
         AggBatch b, AggTableDev t, AggCallDev c0, AggCallDev c1, AggCallDev c2,
-        AggCallDev c3, uint32_t r0, uint32_t r1, uint32_t span_tiles) {
-    agg_apply_dense4_body<n_calls, CS, true>(b, t, c0, c1, c2, c3, r0, r1,
-                                             span_tiles);
+        AggCallDev c3, uint32_t r0, uint32_t r1, uint32_t span_tiles,
+        uint32_t fuse_arg) {
+    // the tail rebuilds its thread index from this scalar and the lane
+    // number, so that no VGPR of the main loop has to carry threadIdx.x
+    const uint32_t wave_id =
+        FUSE ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+             : 0u;
+    agg_apply_dense4_body<n_calls, CS, true, FUSE>(b, t, c0, c1, c2, c3, r0,
+                                                   r1, span_tiles);
+    if constexpr (FUSE) {
+        __shared__ uint32_t s_last;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const AggTableDev tt = span_tail_table();
+        const uint32_t lane = __lane_id();
+        const uint32_t tid = wave_id * 64u + lane;
+        if (tid == 0) {
+            // a launch's blocks end together, and one word takes about 88
+            // returning atomics per microsecond: 2048 tickets on one word
+            // measured 13 us per launch. Blocks draw on one of AGG_FUSE_SHARDS words, each
+            // on a line of its own; a shard's last arriver zeroes it and
+            // draws on the top word.
+            const uint32_t sh = blockIdx.x % AGG_FUSE_SHARDS;
+            const uint32_t members = gridDim.x / AGG_FUSE_SHARDS +
+                                     (sh < gridDim.x % AGG_FUSE_SHARDS ? 1u : 0u);
+            const uint32_t shards =
+                gridDim.x < AGG_FUSE_SHARDS ? gridDim.x : AGG_FUSE_SHARDS;
+            uint32_t* shard = &tt.counters[AGG_CTR_SHARD0 + 32u * sh];
+            bool last = false;
+            if (__hip_atomic_fetch_add(shard, 1u, RLX) == members - 1) {
+                st_u32(shard, 0u);
+                last = __hip_atomic_fetch_add(&tt.counters[4], 1u, RLX) ==
+                       shards - 1;
+            }
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            s_last = last;
+        }
+        __syncthreads();
+        if (!s_last) return;
+        const uint32_t n_dirty = ld_u32(&tt.counters[0]);
+        const uint32_t kinds = fuse_arg & 0xffffu;
+        const int rci = (int)((fuse_arg >> 16) & 0xffu);
+        const size_t cap = (size_t)tt.cap_mask + 1;
+        // four passes' dirty_list loads go out together (a q7 checkpoint has
+        // at most 1024 dirty slots); the state loads of the four passes
+        // together do not fit the kernel's 64 VGPRs
+        for (uint32_t i0 = 0; i0 < n_dirty; i0 += 1024u) {
+            uint32_t slot[4];
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                const uint32_t i = i0 + p * 256u + tid;
+                slot[p] = i < n_dirty ? tt.dirty_list[i] : 0u;
+            }
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                if (i0 + p * 256u >= n_dirty) break; // block-uniform
+                agg_flush_fast_pass<1, n_calls, true>(
+                    tt, rci, kinds, cap, (int)lane, i0 + p * 256u + tid,
+                    n_dirty, slot[p]);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            atomicMax(&tt.counters[5], n_dirty); // high-water mark
+            atomicExch(&tt.counters[0], 0u);     // dirty count
+            atomicExch(&tt.counters[1], 0u);     // out cursor
+            atomicExch(&tt.counters[4], 0u);     // arrival ticket
+        }
+    }
 }
 
 // agg_flush: flush_data's emit-on-update branch (hash_agg.rs:475-501) +
@@ -1689,137 +1821,150 @@ __global__ void agg_flush_kernel(AggTableDev t, int KW, int n_calls,
 //    count before it draws, so the zeros cannot land before a working
 //    block has read it; a block that reads 0 afterwards had no work anyway.
 //    Nothing waits on another block. counters[2] (overflow) stays sticky.
-template <int KW, int NC>
-__global__ __launch_bounds__(256) void agg_flush_fast_kernel(
-        AggTableDev t, int row_count_index, uint32_t kinds, int fused_reset) {
-    const uint32_t n_dirty = __atomic_load_n(&t.counters[0], __ATOMIC_RELAXED);
-    const uint32_t block0 = blockIdx.x * 256u;
-    if (block0 >= n_dirty) return;
-    const uint32_t stride = gridDim.x * 256u;
-    const size_t cap = (size_t)t.cap_mask + 1;
+//  - block 0 records the largest dirty count seen in counters[5].
+//
+// One pass of the fast flush for thread `i` of `n_dirty`; PRELOADED: the
+// caller has read `slot` = dirty_list[i] already. The whole wave calls it
+// together (ballots), threads past the dirty count included. Shared by agg_flush_fast_kernel and the fused tail
+// of agg_apply_dense4_kernel_span.
+template <int KW, int NC, bool PRELOADED>
+__device__ __forceinline__ void agg_flush_fast_pass(
+        const AggTableDev& t, int row_count_index, uint32_t kinds, size_t cap,
+        int lane, uint32_t i, uint32_t n_dirty, uint32_t slot) {
     constexpr int width = KW + NC;
-    const int lane = threadIdx.x & 63;
     const uint64_t lanes_below = (1ull << lane) - 1;
-    for (uint32_t i0 = block0; i0 < n_dirty; i0 += stride) {
-        const uint32_t i = i0 + threadIdx.x;
-        uint32_t slot = 0;
-        long long curr[NC], prevv[NC];
-        uint8_t curr_null[NC], prevn[NC];
-        int64_t key[KW];
-        uint32_t knull = 0;
-        int change = 0; // 0 none, 1 insert, 2 delete, 3 update
-        if (i < n_dirty) {
-            slot = t.dirty_list[i];
-            long long a[NC];
-            uint8_t h[NC];
+    long long curr[NC], prevv[NC];
+    uint8_t curr_null[NC], prevn[NC];
+    int64_t key[KW];
+    uint32_t knull = 0;
+    int change = 0; // 0 none, 1 insert, 2 delete, 3 update
+    if (i < n_dirty) {
+        if (!PRELOADED) slot = t.dirty_list[i];
+        long long a[NC];
+        uint8_t h[NC];
 #pragma unroll
-            for (int ci = 0; ci < NC; ci++) {
-                a[ci] = t.acc[(size_t)ci * cap + slot];
-                h[ci] = t.has[(size_t)ci * cap + slot];
-                prevv[ci] = t.prev[(size_t)ci * cap + slot];
-                prevn[ci] = t.prev_null[(size_t)ci * cap + slot];
+        for (int ci = 0; ci < NC; ci++) {
+            a[ci] = t.acc[(size_t)ci * cap + slot];
+            h[ci] = t.has[(size_t)ci * cap + slot];
+            prevv[ci] = t.prev[(size_t)ci * cap + slot];
+            prevn[ci] = t.prev_null[(size_t)ci * cap + slot];
+        }
+        const uint8_t hp = t.has_prev[slot];
+#pragma unroll
+        for (int k = 0; k < KW; k++) key[k] = t.keys[(size_t)slot * KW + k];
+        knull = t.key_nulls[slot];
+        // row_count_of clamp (agg_group.rs:63-75); prev/prev_null hold
+        // no meaningful value until has_prev is set
+        long long rc = 0, prc = 0;
+#pragma unroll
+        for (int ci = 0; ci < NC; ci++)
+            if (ci == row_count_index) {
+                rc = a[ci];
+                prc = prevv[ci];
             }
-            const uint8_t hp = t.has_prev[slot];
+        if (rc < 0) rc = 0;
+        const long long prev_rc = (hp && prc > 0) ? prc : 0;
+        bool eq = true;
 #pragma unroll
-            for (int k = 0; k < KW; k++) key[k] = t.keys[(size_t)slot * KW + k];
-            knull = t.key_nulls[slot];
-            // row_count_of clamp (agg_group.rs:63-75); prev/prev_null hold
-            // no meaningful value until has_prev is set
-            long long rc = 0, prc = 0;
-#pragma unroll
-            for (int ci = 0; ci < NC; ci++)
-                if (ci == row_count_index) {
-                    rc = a[ci];
-                    prc = prevv[ci];
-                }
-            if (rc < 0) rc = 0;
-            const long long prev_rc = (hp && prc > 0) ? prc : 0;
-            bool eq = true;
+        for (int ci = 0; ci < NC; ci++) {
+            const uint32_t kind = (kinds >> (8 * ci)) & 0xffu;
+            const bool never_null = kind == RW_AGG_COUNT_STAR ||
+                                    kind == RW_AGG_COUNT ||
+                                    kind == RW_AGG_SUM0;
+            curr[ci] = a[ci];
+            curr_null[ci] = never_null ? 0 : !h[ci];
+            eq = eq && prevn[ci] == curr_null[ci] &&
+                 (prevn[ci] || prevv[ci] == curr[ci]);
+        }
+        // infer_change_type (agg_group.rs:138-163)
+        if (prev_rc == 0 && rc == 0) change = 0;
+        else if (prev_rc == 0) change = 1;
+        else if (rc == 0) change = 2;
+        else change = eq ? 0 : 3;
+        if (rc == 0) {
+            // reset value states (agg_state.rs:149-155)
 #pragma unroll
             for (int ci = 0; ci < NC; ci++) {
                 const uint32_t kind = (kinds >> (8 * ci)) & 0xffu;
-                const bool never_null = kind == RW_AGG_COUNT_STAR ||
-                                        kind == RW_AGG_COUNT ||
-                                        kind == RW_AGG_SUM0;
-                curr[ci] = a[ci];
-                curr_null[ci] = never_null ? 0 : !h[ci];
-                eq = eq && prevn[ci] == curr_null[ci] &&
-                     (prevn[ci] || prevv[ci] == curr[ci]);
+                t.acc[(size_t)ci * cap + slot] =
+                    kind == RW_AGG_MIN ? INT64_MAX
+                    : kind == RW_AGG_MAX ? INT64_MIN : 0;
+                t.has[(size_t)ci * cap + slot] = 0;
             }
-            // infer_change_type (agg_group.rs:138-163)
-            if (prev_rc == 0 && rc == 0) change = 0;
-            else if (prev_rc == 0) change = 1;
-            else if (rc == 0) change = 2;
-            else change = eq ? 0 : 3;
-            if (rc == 0) {
-                // reset value states (agg_state.rs:149-155)
+        }
+        t.dirty_flag[slot] = 0;
+    }
+    const int n_out = change == 3 ? 2 : (change ? 1 : 0);
+    const uint64_t b1 = __ballot(n_out >= 1);
+    const uint64_t b2 = __ballot(n_out == 2);
+    const uint32_t wave_rows = __popcll(b1) + __popcll(b2);
+    if (wave_rows) { // wave-uniform
+        uint32_t wbase = 0;
+        if (lane == 0) wbase = atomicAdd(&t.counters[1], wave_rows);
+        wbase = __shfl(wbase, 0);
+        const uint32_t orow = wbase + __popcll(b1 & lanes_below) +
+                              __popcll(b2 & lanes_below);
+        if (n_out && orow + n_out > t.out_capacity) {
+            atomicExch(&t.counters[2], 2u); // output overflow
+        } else if (n_out) {
+            auto write_row = [&](uint32_t r, uint8_t op,
+                                 const long long (&vals)[NC],
+                                 const uint8_t (&nulls)[NC]) {
+                t.out_ops[r] = op;
+                long long* ov = t.out_vals + (size_t)r * width;
+                uint8_t* on = t.out_nulls + (size_t)r * width;
+#pragma unroll
+                for (int k = 0; k < KW; k++) {
+                    ov[k] = key[k];
+                    on[k] = (knull >> k) & 1;
+                }
 #pragma unroll
                 for (int ci = 0; ci < NC; ci++) {
-                    const uint32_t kind = (kinds >> (8 * ci)) & 0xffu;
-                    t.acc[(size_t)ci * cap + slot] =
-                        kind == RW_AGG_MIN ? INT64_MAX
-                        : kind == RW_AGG_MAX ? INT64_MIN : 0;
-                    t.has[(size_t)ci * cap + slot] = 0;
+                    ov[KW + ci] = vals[ci];
+                    on[KW + ci] = nulls[ci];
                 }
+            };
+            if (change == 1) {
+                write_row(orow, RW_OP_INSERT, curr, curr_null);
+            } else if (change == 2) {
+                write_row(orow, RW_OP_DELETE, prevv, prevn);
+            } else {
+                write_row(orow, RW_OP_UPDATE_DELETE, prevv, prevn);
+                write_row(orow + 1, RW_OP_UPDATE_INSERT, curr, curr_null);
             }
-            t.dirty_flag[slot] = 0;
-        }
-        const int n_out = change == 3 ? 2 : (change ? 1 : 0);
-        const uint64_t b1 = __ballot(n_out >= 1);
-        const uint64_t b2 = __ballot(n_out == 2);
-        const uint32_t wave_rows = __popcll(b1) + __popcll(b2);
-        if (wave_rows) { // wave-uniform
-            uint32_t wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&t.counters[1], wave_rows);
-            wbase = __shfl(wbase, 0);
-            const uint32_t orow = wbase + __popcll(b1 & lanes_below) +
-                                  __popcll(b2 & lanes_below);
-            if (n_out && orow + n_out > t.out_capacity) {
-                atomicExch(&t.counters[2], 2u); // output overflow
-            } else if (n_out) {
-                auto write_row = [&](uint32_t r, uint8_t op,
-                                     const long long (&vals)[NC],
-                                     const uint8_t (&nulls)[NC]) {
-                    t.out_ops[r] = op;
-                    long long* ov = t.out_vals + (size_t)r * width;
-                    uint8_t* on = t.out_nulls + (size_t)r * width;
+            // prev := curr (or cleared on delete) — agg_group.rs:571-607
+            if (change == 2) {
+                t.has_prev[slot] = 0;
+            } else {
+                t.has_prev[slot] = 1;
 #pragma unroll
-                    for (int k = 0; k < KW; k++) {
-                        ov[k] = key[k];
-                        on[k] = (knull >> k) & 1;
-                    }
-#pragma unroll
-                    for (int ci = 0; ci < NC; ci++) {
-                        ov[KW + ci] = vals[ci];
-                        on[KW + ci] = nulls[ci];
-                    }
-                };
-                if (change == 1) {
-                    write_row(orow, RW_OP_INSERT, curr, curr_null);
-                } else if (change == 2) {
-                    write_row(orow, RW_OP_DELETE, prevv, prevn);
-                } else {
-                    write_row(orow, RW_OP_UPDATE_DELETE, prevv, prevn);
-                    write_row(orow + 1, RW_OP_UPDATE_INSERT, curr, curr_null);
-                }
-                // prev := curr (or cleared on delete) — agg_group.rs:571-607
-                if (change == 2) {
-                    t.has_prev[slot] = 0;
-                } else {
-                    t.has_prev[slot] = 1;
-#pragma unroll
-                    for (int ci = 0; ci < NC; ci++) {
-                        t.prev[(size_t)ci * cap + slot] = curr[ci];
-                        t.prev_null[(size_t)ci * cap + slot] = curr_null[ci];
-                    }
+                for (int ci = 0; ci < NC; ci++) {
+                    t.prev[(size_t)ci * cap + slot] = curr[ci];
+                    t.prev_null[(size_t)ci * cap + slot] = curr_null[ci];
                 }
             }
         }
     }
+}
+
+template <int KW, int NC>
+__global__ __launch_bounds__(256) void agg_flush_fast_kernel(
+        AggTableDev t, int row_count_index, uint32_t kinds, int fused_reset) {
+    const uint32_t n_dirty = __atomic_load_n(&t.counters[0], __ATOMIC_RELAXED);
+    const uint32_t block0 = blockIdx.x * blockDim.x;
+    if (block0 >= n_dirty) return;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const size_t cap = (size_t)t.cap_mask + 1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&t.counters[5], n_dirty);
+    for (uint32_t i0 = block0; i0 < n_dirty; i0 += stride) {
+        agg_flush_fast_pass<KW, NC>(t, row_count_index, kinds, cap,
+                                    threadIdx.x & 63, i0 + threadIdx.x,
+                                    n_dirty);
+    }
     if (fused_reset) {
         __syncthreads(); // block-uniform: every thread ran the same trip count
         if (threadIdx.x == 0) {
-            uint32_t working = (n_dirty + 255u) / 256u;
+            uint32_t working = (n_dirty + blockDim.x - 1) / blockDim.x;
             if (working > gridDim.x) working = gridDim.x;
             if (atomicAdd(&t.counters[3], 1u) == working - 1) {
                 atomicExch(&t.counters[0], 0u); // dirty count
@@ -2100,6 +2245,53 @@ struct HashAgg {
     }
     uint32_t span_tiles_override = 0; // rw_agg_debug_set_span_tiles
 
+    // Fused checkpoint flush (rw_agg_apply_flush_launch): the
+    // span kernel's last-arriving block runs the flush. ONE block moves a
+    // slot's scattered lines at ~70 GB/s, and on the MI355X that lost to the
+    // flush launch at every dirty count measured (64 groups: +1.4 %, 1024:
+    // +66 %), so the path is OFF unless RW_AGG_FUSE_FLUSH=1 asks for it
+    // (read when the executor is created). Enabled, the dirty-count policy
+    // guards it: the host cannot read the count on the asynchronous path;
+    // every flush records the largest count it has seen in counters[5],
+    // check_overflow() copies it at every sync, and fusion is allowed only
+    // once a sync has shown it at most FUSE_MAX. The mark never falls: one
+    // large flush turns fusion off for good.
+    static constexpr uint32_t FUSE_MAX = 64;
+    bool fuse_env = false; // RW_AGG_FUSE_FLUSH=1
+    int fuse_mode = 0; // rw_agg_debug_set_fuse: 0 policy, 1 always, 2 never
+    bool dirty_hwm_known = false;
+    uint32_t dirty_hwm = 0;
+    uint64_t fused_launches = 0; // rw_agg_debug_fused_launches
+
+    static bool flush_fast_enabled() {
+        static int en = [] {
+            const char* e = getenv("RW_AGG_FLUSH_FAST");
+            return !(e && *e == '0');
+        }();
+        return en;
+    }
+    bool fuse_allowed() const {
+        if (fuse_mode == 2) return false;
+        if (!flush_fast_enabled() || n_dec || n_minput || eowc) return false;
+        if (fuse_mode == 1) return true;
+        return fuse_env && dirty_hwm_known && dirty_hwm <= FUSE_MAX;
+    }
+
+    // apply_range's HIP event pair costs ~5 us of a ~62 us epoch step on
+    // this runtime: it is recorded on one launch in
+    // 16, the first after a stats reset included, and only recorded
+    // launches count in apply_launches / apply_rows / apply_ms_total, so the
+    // averages stay averages (A/B via RW_AGG_EVENT_EVERY=1).
+    static uint32_t ev_every() {
+        static uint32_t n = [] {
+            const char* e = getenv("RW_AGG_EVENT_EVERY");
+            int v = e ? atoi(e) : 0;
+            return (uint32_t)(v > 0 ? v : 16);
+        }();
+        return n;
+    }
+    uint32_t ev_seq = 0;
+
     AggCallDev cd(int i) const {
         if (i < n_calls) {
             int8_t mord = 0, dord = 0;
@@ -2117,6 +2309,7 @@ struct HashAgg {
         if (!gpu_ok()) FAIL(RW_E_NOGPU, "risingwave_amd: no GPU visible (product path has no CPU fallback)");
         desc = *d;
         eowc = d->emit_on_window_close != 0;
+        if (const char* e = getenv("RW_AGG_FUSE_FLUSH")) fuse_env = *e == '1';
         input_types.assign(d->input_types, d->input_types + d->n_input_cols);
         group_key.assign(d->group_key_indices, d->group_key_indices + d->n_group_key);
         calls.assign(d->calls, d->calls + d->n_calls);
@@ -2223,8 +2416,8 @@ struct HashAgg {
         HIP_TRY(hipMalloc(&t.dirty_flag, cap * 4));
         HIP_TRY(hipMemset(t.dirty_flag, 0, cap * 4));
         HIP_TRY(hipMalloc(&t.dirty_list, cap * 4));
-        HIP_TRY(hipMalloc(&t.counters, 4 * 4));
-        HIP_TRY(hipMemset(t.counters, 0, 4 * 4));
+        HIP_TRY(hipMalloc(&t.counters, AGG_CTR_WORDS * 4));
+        HIP_TRY(hipMemset(t.counters, 0, AGG_CTR_WORDS * 4));
         t.out_capacity = 1u << 22;
         HIP_TRY(hipMalloc(&t.out_vals, (size_t)t.out_capacity * out_width * 8));
         HIP_TRY(hipMalloc(&t.out_nulls, (size_t)t.out_capacity * out_width));
@@ -2372,7 +2565,10 @@ struct HashAgg {
         return RW_OK;
     }
 
-    void launch_apply(const AggBatch& b, uint32_t r0, uint32_t r1) {
+    // `fuse`: carry the checkpoint flush in the launch where the launch is
+    // a span one; returns whether it did.
+    bool launch_apply(const AggBatch& b, uint32_t r0, uint32_t r1,
+                      bool fuse = false) {
         auto a0 = cd(0), a1 = cd(1), a2 = cd(2), a3 = cd(3);
         if (b.dense && KW == 1 && b.stride == 1 && n_minput == 0 &&
             n_dec == 0 && distinct_slots.empty() &&
@@ -2395,12 +2591,21 @@ struct HashAgg {
                                               : span_tiles_for(r1 - r0, grid);
             uint32_t waves = (tiles + st - 1) / st;
             int sgrid = (int)((waves + 3) / 4);
+            // the fused tail's flush arguments: call kinds one per byte,
+            // row_count_index above them
+            uint32_t farg = (uint32_t)desc.row_count_index << 16;
+            for (int ci = 0; ci < n_calls && ci < 2; ci++)
+                farg |= (uint32_t)calls[ci].kind << (8 * ci);
             #define RW_DCS(nc, csv)                                           \
                 do {                                                          \
-                    if (span_en)                                              \
+                    if (span_en && fuse)                                      \
+                        agg_apply_dense4_kernel_span<nc, csv, true>           \
+                            <<<sgrid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, \
+                                                        r0, r1, st, farg);    \
+                    else if (span_en)                                         \
                         agg_apply_dense4_kernel_span<nc, csv>                 \
                             <<<sgrid, 256, 0, stream>>>(b, t, a0, a1, a2, a3, \
-                                                        r0, r1, st);          \
+                                                        r0, r1, st, 0u);      \
                     else                                                      \
                         agg_apply_dense4_kernel_w8<nc, csv>                   \
                             <<<grid, 256, 0, stream>>>(b, t, a0, a1, a2, a3,  \
@@ -2413,15 +2618,15 @@ struct HashAgg {
             // way round) have the CS kernels; every other shape, count-star
             // with 3 or 4 calls included, takes the generic one
             switch (cs < 0 ? -1 : n_calls * 8 + cs) {
-                case 1 * 8 + 0: RW_DCS(1, 0); return;
-                case 2 * 8 + 0: RW_DCS(2, 0); return;
-                case 2 * 8 + 1: RW_DCS(2, 1); return;
+                case 1 * 8 + 0: RW_DCS(1, 0); return span_en && fuse;
+                case 2 * 8 + 0: RW_DCS(2, 0); return span_en && fuse;
+                case 2 * 8 + 1: RW_DCS(2, 1); return span_en && fuse;
             }
             switch (n_calls) {
-                case 1: RW_DENSE(1); return;
-                case 2: RW_DENSE(2); return;
-                case 3: RW_DENSE(3); return;
-                case 4: RW_DENSE(4); return;
+                case 1: RW_DENSE(1); return false;
+                case 2: RW_DENSE(2); return false;
+                case 3: RW_DENSE(3); return false;
+                case 4: RW_DENSE(4); return false;
             }
             #undef RW_DCS
             #undef RW_DENSE
@@ -2455,6 +2660,7 @@ struct HashAgg {
             case 4 * 8 + 4: RW_LAUNCH(4, 4); break;
         }
         #undef RW_LAUNCH
+        return false;
     }
 
     int apply(const AggBatch& b, bool timed,
@@ -2488,8 +2694,11 @@ struct HashAgg {
 
     // apply a sub-range of a device batch as one launch (epoch-granular
     // ingestion: chunks buffered within an epoch are applied together)
-    int apply_range(const AggBatch& b, uint32_t r0, uint32_t r1, bool timed) {
+    // `fuse`/`fused`: as launch_apply's flag and result.
+    int apply_range(const AggBatch& b, uint32_t r0, uint32_t r1, bool timed,
+                    bool fuse = false, bool* fused = nullptr) {
         int slot = -1;
+        timed = timed && ev_seq++ % ev_every() == 0;
         if (timed) {
             slot = (int)(ev_head++ % EV_RING);
             if (!ev0[slot]) {
@@ -2499,7 +2708,9 @@ struct HashAgg {
             if (ev_harvest(slot) != RW_OK) return RW_E_INTERNAL;
             HIP_TRY(hipEventRecord(ev0[slot], stream));
         }
-        launch_apply(b, r0, r1);
+        bool did = launch_apply(b, r0, r1, fuse);
+        if (fused) *fused = did;
+        fused_launches += did;
         if (timed) {
             HIP_TRY(hipEventRecord(ev1[slot], stream));
             ev_pending[slot] = 1;
@@ -2700,8 +2911,10 @@ struct HashAgg {
     }
 
     int check_overflow() {
-        uint32_t ctr[3];
-        HIP_TRY(hipMemcpy(ctr, t.counters, 12, hipMemcpyDeviceToHost));
+        uint32_t ctr[6];
+        HIP_TRY(hipMemcpy(ctr, t.counters, 24, hipMemcpyDeviceToHost));
+        dirty_hwm = ctr[5]; // fuse_allowed()
+        dirty_hwm_known = true;
         if (ctr[2] == 1) FAIL(RW_E_INTERNAL, "agg state table full (capacity %u)", capacity);
         if (ctr[2] == 2) FAIL(RW_E_INTERNAL, "agg output buffer overflow");
         if (ctr[2] == 3) FAIL(RW_E_INTERNAL, "agg minput row store full");
@@ -2754,25 +2967,31 @@ struct HashAgg {
     // (the host-synchronous paths), or -1 on the stream-ordered path, which
     // also wants counters[0..1] zeroed behind the flush (`stream_reset`).
     // Value-state executors take agg_flush_fast_kernel: the grid is sized
-    // to the count when it is known; unknown, 512 blocks cover 128K slots
-    // per grid-stride pass, blocks past the dirty count exit on their first
-    // load, and at most 512 blocks ever draw a reset ticket. Decimal and
+    // to the count when it is known; unknown, 2048 one-wave blocks cover
+    // 128K slots per grid-stride pass, blocks past the dirty count exit on
+    // their first load, and at most 2048 blocks ever draw a reset ticket. Decimal and
     // materialized-input executors, or RW_AGG_FLUSH_FAST=0 (A/B), keep the
     // generic kernel at its fixed grid with the separate reset launch.
     void launch_flush(long long n_dirty, bool stream_reset) {
-        static int fast_en = [] {
-            const char* e = getenv("RW_AGG_FLUSH_FAST");
-            return !(e && *e == '0');
-        }();
-        if (fast_en && n_dec == 0 && n_minput == 0) {
+        if (flush_fast_enabled() && n_dec == 0 && n_minput == 0) {
             if (n_dirty == 0) return; // counters already read back as idle
-            int grid = n_dirty < 0 ? 512 : grid_for((uint32_t)n_dirty);
+            // One-wave blocks: a slot's state is a dozen scattered lines, and
+            // one CU moves only ~70 GB/s of those (a 256-slot block takes
+            // ~8 us), so a q7 checkpoint's 1024 slots go to 16
+            // CUs instead of 4. Thread counts are as with 256-thread blocks
+            // (A/B via RW_AGG_FLUSH_BLOCK=256).
+            static int bs = [] {
+                const char* e = getenv("RW_AGG_FLUSH_BLOCK");
+                return e && atoi(e) == 256 ? 256 : 64;
+            }();
+            int grid = (n_dirty < 0 ? 512 : grid_for((uint32_t)n_dirty)) *
+                       (256 / bs);
             uint32_t kinds = 0;
             for (int ci = 0; ci < n_calls; ci++)
                 kinds |= (uint32_t)calls[ci].kind << (8 * ci);
             #define RW_FF(kw, nc)                                              \
                 case kw * 8 + nc:                                              \
-                    agg_flush_fast_kernel<kw, nc><<<grid, 256, 0, stream>>>(   \
+                    agg_flush_fast_kernel<kw, nc><<<grid, bs, 0, stream>>>(    \
                         t, (int)desc.row_count_index, kinds,                   \
                         stream_reset ? 1 : 0);                                 \
                     return;
@@ -3813,6 +4032,8 @@ int rw_agg_bench_apply(void* h, void* batch) {
 }
 
 int rw_agg_flush_launch(void* h, uint64_t epoch); // defined below
+int rw_agg_apply_flush_launch(void* h, void* batch, uint32_t r0, uint32_t r1,
+                              uint64_t epoch); // defined below
 
 // C-side step loop: the Python interpreter costs ~15-20 us per step at q7
 // sizes (ctypes + loop bookkeeping), which exceeds the 16 us apply kernel
@@ -3842,8 +4063,6 @@ int rw_agg_bench_run(void* h, void** batches, int n_batches, int steps,
 int rw_agg_bench_run_epochs(void* h, void* giant, uint64_t rows_per_step,
                             int n_slots, int steps, int barrier_every,
                             int step0) {
-    auto* agg = (HashAgg*)h;
-    auto* b = (AggBatch*)giant;
     if (barrier_every <= 0 || n_slots % barrier_every ||
         step0 % barrier_every)
         FAIL(RW_E_INVAL, "epoch run needs barrier_every | n_slots, aligned step0");
@@ -3851,9 +4070,8 @@ int rw_agg_bench_run_epochs(void* h, void* giant, uint64_t rows_per_step,
         int width = steps - s < barrier_every ? steps - s : barrier_every;
         uint32_t r0 = (uint32_t)(((step0 + s) % n_slots) * rows_per_step);
         uint32_t r1 = r0 + (uint32_t)(width * rows_per_step);
-        int rc = agg->apply_range(*b, r0, r1, true);
-        if (rc != RW_OK) return rc;
-        rc = rw_agg_flush_launch(h, (uint64_t)(step0 + s));
+        int rc = rw_agg_apply_flush_launch(h, giant, r0, r1,
+                                           (uint64_t)(step0 + s));
         if (rc != RW_OK) return rc;
     }
     return RW_OK;
@@ -3968,6 +4186,25 @@ int rw_agg_flush_launch(void* h, uint64_t epoch) {
     return RW_OK;
 }
 
+// one epoch, fully async: apply rows [r0, r1) of a preloaded batch and run
+// the checkpoint flush behind it. Leaves the executor as apply_range +
+// rw_agg_flush_launch leave it; where HashAgg::fuse_allowed and the launch
+// shape permit, the flush runs in the apply launch's last-arriving block
+// instead of a launch of its own (only with RW_AGG_FUSE_FLUSH=1: measured
+// slower than two launches on the MI355X).
+int rw_agg_apply_flush_launch(void* h, void* batch, uint32_t r0, uint32_t r1,
+                              uint64_t epoch) {
+    auto* agg = (HashAgg*)h;
+    auto* b = (AggBatch*)batch;
+    if (r0 > r1 || r1 > b->n_rows)
+        FAIL(RW_E_INVAL, "apply range [%u, %u) outside the batch's %u rows", r0,
+             r1, b->n_rows);
+    bool fused = false;
+    int rc = agg->apply_range(*b, r0, r1, true, agg->fuse_allowed(), &fused);
+    if (rc != RW_OK) return rc;
+    return fused ? RW_OK : rw_agg_flush_launch(h, epoch);
+}
+
 int rw_agg_kernel_stats(void* h, RwKernelStats* out) {
     auto* agg = (HashAgg*)h;
     if (agg->ev_harvest_all() != RW_OK)
@@ -3993,6 +4230,25 @@ int rw_agg_debug_set_span_tiles(void* h, uint32_t n) {
     ((HashAgg*)h)->span_tiles_override = n;
     return RW_OK;
 }
+
+// debug: the fused checkpoint flush of rw_agg_apply_flush_launch: 0 = the
+// dirty-count policy (HashAgg::fuse_allowed), 1 = always where the launch is
+// eligible, 2 = never
+int rw_agg_debug_set_fuse(void* h, int mode) {
+    if (mode < 0 || mode > 2) FAIL(RW_E_INVAL, "fuse mode %d (0..2)", mode);
+    ((HashAgg*)h)->fuse_mode = mode;
+    return RW_OK;
+}
+
+// debug: would an eligible launch fuse right now; how many launches have
+// carried the flush so far; the policy's dirty-count limit
+int rw_agg_debug_fuse_allowed(void* h) {
+    return ((HashAgg*)h)->fuse_allowed() ? 1 : 0;
+}
+long long rw_agg_debug_fused_launches(void* h) {
+    return (long long)((HashAgg*)h)->fused_launches;
+}
+uint32_t rw_agg_debug_fuse_max(void) { return HashAgg::FUSE_MAX; }
 
 int rw_agg_debug_scan(void* h, RwAggDebug* out) {
     auto* agg = (HashAgg*)h;
@@ -4163,6 +4419,7 @@ int rw_agg_stats_reset(void* h) {
     agg->apply_launches = 0;
     agg->apply_ms_total = 0;
     agg->apply_rows = 0;
+    agg->ev_seq = 0;
     return RW_OK;
 }
 
