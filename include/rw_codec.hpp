@@ -260,6 +260,35 @@ inline size_t value_decode_str(const uint8_t* p, size_t avail, bool* null,
     return 5 + (size_t)n;
 }
 
+// Memcomparable varchar datum, ASC NULLS LAST (the only order state-table
+// group keys use): the null tag byte, then for a non-null string one byte
+// 0x00 (empty) or 0x01, then the bytes in zero-padded groups of 8, each
+// group followed by one byte: 9 when more data follows, else the count
+// (1..8) of significant bytes in this last group. A restatement of the
+// memcomparable crate's serialize_bytes FROM MEMORY — the crate is not
+// vendored here and this form is unverified against it.
+// What tests/agg_varchar_host_check.cpp does verify: byte-string order is
+// preserved and the encoding is injective.
+inline void memcmp_encode_str(std::vector<uint8_t>& buf, bool null,
+                              const uint8_t* s, uint32_t len) {
+    if (null) {
+        buf.push_back(1);
+        return;
+    }
+    buf.push_back(0);
+    if (len == 0) {
+        buf.push_back(0);
+        return;
+    }
+    buf.push_back(1);
+    for (uint32_t off = 0; off < len; off += 8) {
+        uint32_t take = len - off < 8 ? len - off : 8;
+        for (uint32_t k = 0; k < 8; k++)
+            buf.push_back(k < take ? s[off + k] : 0);
+        buf.push_back(off + 8 < len ? 9 : (uint8_t)take);
+    }
+}
+
 // iterate spill frames ([put u8][klen u32 LE][key][vlen u32 LE][value]);
 // calls fn(put, key_ptr, klen, val_ptr, vlen); returns false on malformed
 template <typename F>

@@ -358,7 +358,7 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed);
  *    the block layout of include/rw_xpayload.hpp.
  *    Out of scope: device-resident join ingest of a received payload (the
  *    join consumes host chunks via push_chunk), varchar in
- *    rw_agg_apply_payload / HashAgg, rw_join_vnode_hop on a varchar join,
+ *    rw_agg_apply_payload, rw_join_vnode_hop on a varchar join,
  *    and the U-pair downgrade inside the device partition.
  *
  * rw_hash_join_varlen_reserve sets `side`'s initial arena capacity in
@@ -376,6 +376,62 @@ int rw_hash_join_varlen_stats(void* h, int side, uint64_t* used,
  * share, `bytes` = packed output bytes, `launches` = materialisations. */
 int rw_hash_join_varlen_emit_stats(void* h, double* ms, double* copy_ms,
                                    uint64_t* bytes, uint64_t* launches);
+/* ----- varchar GROUP KEYS in HashAgg -----
+ * RwHashAggDesc does not change: input_types[k] == RW_T_VARCHAR on a
+ * group-key column is the whole switch. The executor owns one device
+ * string-interning table (byte string -> one canonical reference word)
+ * and one append-only byte arena holding every distinct string it has
+ * seen, once; each pushed batch is interned before the apply launch, so
+ * the agg kernels key on words as they do for i64. The arena holds at most
+ * 2^39 bytes (offset bit 39 marks a not-yet-interned word, rw_varlen.hpp).
+ * Strings of groups that died are NOT reclaimed.
+ *  - Supported: varchar in any of the 1..4 group-key positions, mixed with
+ *    i64/ts keys; count(*), count/sum/sum0 on i64/ts/decimal arguments
+ *    (with retractions), append-only min/max.
+ *  - Output key columns come back as RW_T_VARCHAR (RwVarlenData, offsets
+ *    rebased per chunk, NULL rows zero length; rw_chunk_free releases them).
+ *  - Spill keys hold the memcomparable string datum (rw_codec.hpp
+ *    memcmp_encode_str; a restatement unverified against the crate), spill
+ *    values the value-encoded one; rw_hash_agg_restore decodes the strings
+ *    and interns them again.
+ *  - rw_hash_agg_watermark works on a fixed-width key position next to
+ *    varchar ones; on a varchar position it returns RW_E_INVAL.
+ *  - A malformed offsets array, a string over 2^24-1 bytes, or NULL `bytes`
+ *    with a non-zero total fails the push with RW_E_INVAL before any state
+ *    changes.
+ *  - rw_hash_agg_create returns NULL when a group key is varchar and the
+ *    plan has a materialized-input min/max (!append_only), a DISTINCT call,
+ *    or emit_on_window_close; varchar agg arguments and (materialized-
+ *    input) stream keys are rejected as before.
+ *  - RW_E_INVAL on such an executor (they move 8-byte words with no arena
+ *    behind them): rw_hash_agg_ingest_mode(h, 1),
+ *    rw_hash_agg_update_vnode_bitmap, rw_agg_bench_preload (NULL) / apply /
+ *    run / run_epochs, rw_agg_apply_payload, rw_agg_apply_joinout,
+ *    rw_join_apply_aggout, rw_agg_flush_launch, rw_agg_apply_flush_launch,
+ *    rw_q7pipe_bench_run.
+ *
+ * rw_hash_agg_varlen_reserve sets the initial arena capacity in bytes and
+ * the number of distinct strings the table is first sized for (its slot
+ * count is the next power of two >= 2 * n_strings); 0 keeps a default
+ * (1 MiB, 32768 strings). Small values are honoured; both grow by doubling.
+ * Legal only before the first push or restore, and only with a varchar
+ * group key (RW_E_INVAL otherwise). rw_hash_agg_varlen_stats synchronises
+ * and reports exact values: arena bytes used (the reserved header
+ * included) and allocated, distinct strings interned, table slots — all 0
+ * for an executor without varchar group keys or before its first input. */
+int rw_hash_agg_varlen_reserve(void* h, uint64_t arena_bytes,
+                               uint64_t n_strings);
+int rw_hash_agg_varlen_stats(void* h, uint64_t* arena_used,
+                             uint64_t* arena_cap, uint64_t* n_strings,
+                             uint64_t* table_cap);
+/* Cumulative device time of the interning pre-pass since create, measured
+ * only when RW_AGG_INTERN_TIMING=1 was set at create (an event per kernel
+ * boundary, read back where the push synchronises anyway;
+ * tests/bench_varchar_agg.py): kernel_ms[0..2] = lookup, commit, resolve
+ * over `launches` pre-passes; fetch_ms = the flush / clean string
+ * materialisation (length + scan + copy per varchar key column). */
+int rw_hash_agg_varlen_intern_stats(void* h, double* kernel_ms,
+                                    double* fetch_ms, uint64_t* launches);
 /* Same reclamation for the agg's materialized-input row store and the
  * GroupTopN record store (retractions retire rows in place). Same
  * contract: call after the drains; fails loudly on pending deltas. */

@@ -24,6 +24,19 @@ constexpr uint64_t OFF_BITS = 40;
 constexpr uint64_t MAX_OFF = (1ULL << OFF_BITS) - 1; // 2^40-1
 constexpr uint32_t MAX_LEN = (1u << 24) - 1;         // 2^24-1
 
+// HashAgg varchar group keys. A group-key word is CANONICAL:
+// one word per distinct string, referencing the executor's interning arena.
+// While a pushed batch is being interned its words are PROVISIONAL: offset
+// bit 39 set, the remaining offset bits indexing the executor's staging
+// buffer. The bit halves the offset range, so an interning arena (and a
+// staged chunk) holds at most 2^39 bytes. The arena's first
+// AGG_ARENA_HEADER bytes are reserved so that no canonical word is 0 (the
+// NULL / empty-slot word); strings are packed at AGG_ARENA_ALIGN.
+constexpr uint64_t PROV_BIT = 1ULL << 39;
+constexpr uint64_t AGG_ARENA_MAX = PROV_BIT;
+constexpr uint64_t AGG_ARENA_HEADER = 8;
+constexpr uint64_t AGG_ARENA_ALIGN = 1;
+
 RW_VARLEN_HD inline uint64_t pack(uint64_t off, uint32_t len) {
     return (off & MAX_OFF) | ((uint64_t)len << OFF_BITS);
 }

@@ -2161,6 +2161,201 @@ __global__ void agg_minput_restore_kernel(AggTableDev t, int KW, int mord,
     }
 }
 
+// ============ varchar: the string materialiser both executors share ======
+
+// n reference words, word i at words[i * stride] (stride in 8-byte units:
+// 1 for a columnar block, row_stride / 8 for a column of packed records).
+// Optional masks yield the zero word (length 0): nulls[i] != 0 (the join
+// output block's NULL flags) and ops[i] == 0xFF for i < sparse_n (the inner
+// probe's pre-assigned sparse region — those slots hold unwritten words).
+struct VarlenView {
+    const uint64_t* words;
+    uint32_t stride;
+    const uint8_t* nulls;
+    const uint8_t* ops;
+    uint32_t sparse_n;
+};
+
+// Materialises the strings a view's words reference into one packed host
+// byte buffer (length kernel -> rocPRIM exclusive scan -> copy kernel ->
+// D2H), with the device scratch that sequence needs. One per executor
+// (HashJoin's emit/drain/compaction, HashAgg's flush/spill/watermark); the
+// methods are defined beside the kernels.
+struct VarlenFetch {
+    uint64_t* d_vlens = nullptr;
+    uint64_t* d_voffs = nullptr;
+    uint32_t d_vcap = 0;
+    uint8_t* d_vbytes = nullptr;
+    uint64_t d_vbytes_cap = 0;
+    void* d_scan_tmp = nullptr;
+    size_t d_scan_tmp_cap = 0;
+    hipEvent_t vev0 = nullptr, vev1 = nullptr, vev2 = nullptr;
+    double vemit_ms = 0, vcopy_ms = 0; // whole materialise / copy kernel
+    uint64_t vemit_bytes = 0, vemit_launches = 0;
+
+    int ensure_vscratch(uint32_t n);
+    int fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
+              std::vector<uint64_t>& offs, std::vector<uint8_t>& bytes,
+              bool timed, hipStream_t stream);
+    ~VarlenFetch();
+};
+
+// ============ HashAgg varchar group keys: string interning ===
+//
+// A varchar group-key cell is a reference word (rw_varlen.hpp). The agg
+// kernels key on words, so before the apply launch every word of the batch
+// is made CANONICAL: equal strings carry equal words, and the tuned
+// apply / flush / clean / restore kernels run as they do for i64 keys.
+//
+// The table is open-addressed, one 8-byte canonical word per slot, 0 =
+// empty. Visibility rule (guide G16, and the comment above
+// table_find_or_insert): a lane may not read BYTES another lane wrote in
+// the same launch without a release/acquire pair. So every byte a lane
+// hashes or compares was written before its launch began — arena bytes by
+// an earlier launch, staging bytes by the push's host-to-device copy — and
+// only slot WORDS are exchanged in-launch, through relaxed agent-scope
+// atomics. That takes three launch-separated kernels per push:
+//   lookup : CAS the row's provisional (staging) word into an empty slot,
+//            or compare bytes with the word found there; record the slot
+//   commit : one lane per CAS winner appends its string to the arena and
+//            stores the final word into the slot
+//   resolve: every row reloads slot[its recorded index] into the batch
+// No CLAIMED state, no fences.
+struct InternDev {
+    uint64_t* slots;
+    uint32_t cap_mask;
+    uint8_t* arena;
+    uint64_t arena_cap;
+    const uint8_t* stg;       // this push's staged bytes
+    unsigned long long* tail; // arena append cursor (bytes)
+    uint32_t* ctr;            // [0] winners of this push, [1] table entries
+    uint32_t* winners;        // slot indices claimed by this push
+    uint32_t* rowslot;        // per (vcol, row): slot, UINT32_MAX = none
+    uint32_t* err;            // &AggTableDev::counters[2]
+};
+
+// the words to intern: varchar column j of row r at words[j][r * stride];
+// word 0 (NULL) and invisible rows are skipped
+struct InternCols {
+    int64_t* words[MAX_KW];
+    const uint8_t* vis; // may be null
+    uint32_t n_rows, nv, stride;
+};
+
+#define AGG_ERR_INTERN 6u // counters[2] code: intern table / arena full
+
+__device__ __forceinline__ uint64_t intern_hash(const uint8_t* p,
+                                                uint32_t len) {
+    uint64_t h = 0xcbf29ce484222325ULL ^ len; // FNV-1a, then the finalizer
+    for (uint32_t k = 0; k < len; k++) h = (h ^ p[k]) * 0x100000001b3ULL;
+    return mix64(h);
+}
+
+__global__ __launch_bounds__(256) void agg_intern_lookup_kernel(InternDev d,
+                                                                InternCols c) {
+    uint32_t total = c.n_rows * c.nv;
+    uint32_t gstride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += gstride) {
+        uint32_t j = i / c.n_rows, r = i - j * c.n_rows;
+        uint64_t w = (uint64_t)c.words[j][(size_t)r * c.stride];
+        uint32_t found = UINT32_MAX;
+        if (w != 0 && !(c.vis && !c.vis[r])) {
+            uint32_t len = rwvarlen::word_len(w);
+            const uint8_t* p =
+                d.stg + (rwvarlen::word_off(w) & ~rwvarlen::PROV_BIT);
+            uint32_t slot = (uint32_t)intern_hash(p, len) & d.cap_mask;
+            for (uint32_t probes = 0; probes <= d.cap_mask; probes++) {
+                uint64_t cur = __hip_atomic_load(&d.slots[slot], RLX);
+                if (cur == 0) {
+                    cur = atomicCAS((unsigned long long*)&d.slots[slot], 0ULL,
+                                    (unsigned long long)w);
+                    if (cur == 0) { // this row's staged copy is the candidate
+                        d.winners[atomicAdd(&d.ctr[0], 1u)] = slot;
+                        found = slot;
+                        break;
+                    }
+                }
+                // a final word references the arena, a provisional one this
+                // push's staging: both written before this launch
+                if (rwvarlen::word_len(cur) == len) {
+                    uint64_t off = rwvarlen::word_off(cur);
+                    const uint8_t* q = (off & rwvarlen::PROV_BIT)
+                                           ? d.stg + (off & ~rwvarlen::PROV_BIT)
+                                           : d.arena + off;
+                    bool eq = true;
+                    for (uint32_t k = 0; eq && k < len; k++) eq = p[k] == q[k];
+                    if (eq) {
+                        found = slot;
+                        break;
+                    }
+                }
+                slot = (slot + 1) & d.cap_mask;
+            }
+            if (found == UINT32_MAX) st_u32(d.err, AGG_ERR_INTERN); // wrapped
+        }
+        d.rowslot[i] = found;
+    }
+}
+
+__global__ __launch_bounds__(256) void agg_intern_commit_kernel(InternDev d) {
+    uint32_t nw = d.ctr[0]; // final since the lookup launch ended
+    uint32_t gstride = gridDim.x * blockDim.x;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < nw;
+         k += gstride) {
+        uint32_t slot = d.winners[k];
+        uint64_t w = d.slots[slot];
+        uint32_t len = rwvarlen::word_len(w);
+        uint64_t off = atomicAdd(d.tail, (unsigned long long)len);
+        if (off + len > d.arena_cap) { // host bound violated: never write
+            st_u32(d.err, AGG_ERR_INTERN);
+            continue;
+        }
+        const uint8_t* src =
+            d.stg + (rwvarlen::word_off(w) & ~rwvarlen::PROV_BIT);
+        uint8_t* dst = d.arena + off;
+        for (uint32_t b = 0; b < len; b++) dst[b] = src[b];
+        __hip_atomic_store(&d.slots[slot], rwvarlen::pack(off, len), RLX);
+        atomicAdd(&d.ctr[1], 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void agg_intern_resolve_kernel(
+    InternDev d, InternCols c) {
+    uint32_t total = c.n_rows * c.nv;
+    uint32_t gstride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += gstride) {
+        uint32_t j = i / c.n_rows, r = i - j * c.n_rows;
+        uint32_t s = d.rowslot[i];
+        c.words[j][(size_t)r * c.stride] =
+            s == UINT32_MAX ? 0 : (int64_t)d.slots[s];
+    }
+}
+
+// table growth: every entry is distinct, so CAS-on-empty with no compares;
+// the bytes hashed were written by earlier launches
+__global__ __launch_bounds__(256) void agg_intern_rehash_kernel(
+    const uint64_t* old_slots, uint32_t old_cap, uint64_t* slots,
+    uint32_t cap_mask, const uint8_t* arena) {
+    uint32_t gstride = gridDim.x * blockDim.x;
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < old_cap;
+         s += gstride) {
+        uint64_t w = old_slots[s];
+        if (w == 0) continue;
+        uint32_t slot = (uint32_t)intern_hash(arena + rwvarlen::word_off(w),
+                                              rwvarlen::word_len(w)) &
+                        cap_mask;
+        for (uint32_t probes = 0; probes <= cap_mask; probes++) {
+            if (__hip_atomic_load(&slots[slot], RLX) == 0 &&
+                atomicCAS((unsigned long long*)&slots[slot], 0ULL,
+                          (unsigned long long)w) == 0)
+                break;
+            slot = (slot + 1) & cap_mask;
+        }
+    }
+}
+
 struct HashAgg {
     RwHashAggDesc desc;
     std::vector<uint8_t> input_types;
@@ -2232,6 +2427,258 @@ struct HashAgg {
         uint32_t blocks = (work + 255) / 256;
         if (blocks > 2048) blocks = 2048; // G11: cap + grid-stride
         return (int)(blocks ? blocks : 1);
+    }
+
+    // ----- varchar group keys: interning state -----
+    uint32_t vc_mask = 0; // bit i: group-key position i is varchar
+    int nv = 0;           // number of varchar key positions
+    int vpos[MAX_KW] = {};
+    bool has_vc() const { return vc_mask != 0; }
+    static constexpr uint64_t IN_ARENA_DEFAULT = 1ull << 20;
+    static constexpr uint32_t IN_STRINGS_DEFAULT = 1u << 15;
+    InternDev in{};
+    bool in_ready = false;
+    uint8_t* in_stg = nullptr;
+    uint64_t in_stg_cap = 0;
+    uint32_t in_row_cap = 0;
+    uint64_t in_reserve_arena = 0, in_reserve_strings = 0;
+    // The host learns the arena tail and the entry count exactly wherever
+    // it synchronises anyway (flush); between those points it bounds them
+    // by the bytes / rows pushed since.
+    uint64_t in_tail_known = rwvarlen::AGG_ARENA_HEADER, in_tail_pending = 0;
+    uint64_t in_n_known = 0, in_n_pending = 0;
+    // host staging of a batch's provisional words; lives until the next
+    // upload so the async H2D copy never outlives its source
+    std::vector<int64_t> vwords[MAX_KW];
+    // flush / clean materialisation: per key position, n + 1 offsets and
+    // the packed bytes of the rows being emitted or spilled
+    VarlenFetch vf;
+    std::vector<uint64_t> vk_offs[MAX_KW];
+    std::vector<uint8_t> vk_bytes[MAX_KW];
+
+    int intern_init() {
+        if (in_ready) return RW_OK;
+        uint64_t acap = in_reserve_arena ? in_reserve_arena : IN_ARENA_DEFAULT;
+        if (acap < rwvarlen::AGG_ARENA_HEADER) acap = rwvarlen::AGG_ARENA_HEADER;
+        uint64_t want = 2 * (in_reserve_strings ? in_reserve_strings
+                                                : IN_STRINGS_DEFAULT);
+        uint32_t tcap = 2;
+        while (tcap < want && tcap < (1u << 31)) tcap <<= 1;
+        HIP_TRY(hipMalloc(&in.arena, acap));
+        HIP_TRY(hipMemset(in.arena, 0, rwvarlen::AGG_ARENA_HEADER));
+        in.arena_cap = acap;
+        HIP_TRY(hipMalloc(&in.slots, (size_t)tcap * 8));
+        HIP_TRY(hipMemset(in.slots, 0, (size_t)tcap * 8));
+        in.cap_mask = tcap - 1;
+        HIP_TRY(hipMalloc(&in.tail, 8));
+        unsigned long long t0 = rwvarlen::AGG_ARENA_HEADER;
+        HIP_TRY(hipMemcpy(in.tail, &t0, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(&in.ctr, 8));
+        HIP_TRY(hipMemset(in.ctr, 0, 8));
+        in.err = &t.counters[2];
+        in_ready = true;
+        return RW_OK;
+    }
+
+    // exact tail and entry count; the caller has work pending on the stream
+    // or not — either way this drains it
+    int intern_sync_counts() {
+        if (!in_ready) return RW_OK;
+        HIP_TRY(hipStreamSynchronize(stream));
+        unsigned long long tl = 0;
+        uint32_t c[2] = {0, 0};
+        HIP_TRY(hipMemcpy(&tl, in.tail, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, in.ctr, 8, hipMemcpyDeviceToHost));
+        in_tail_known = tl;
+        in_tail_pending = 0;
+        in_n_known = c[1];
+        in_n_pending = 0;
+        return RW_OK;
+    }
+
+    // room for `extra` more arena bytes: reallocate + one D2D copy between
+    // launches (words are offsets, so none is rewritten)
+    int intern_arena_ensure(uint64_t extra) {
+        if (in_tail_known + in_tail_pending + extra <= in.arena_cap)
+            return RW_OK;
+        int rc = intern_sync_counts(); // also: launches may read the old one
+        if (rc != RW_OK) return rc;
+        uint64_t need = in_tail_known + extra;
+        if (need > rwvarlen::AGG_ARENA_MAX)
+            FAIL(RW_E_INVAL, "varchar group-key arena would exceed 2^39 bytes");
+        if (need > in.arena_cap) {
+            uint64_t cap = in.arena_cap;
+            while (cap < need) cap *= 2;
+            uint8_t* na = nullptr;
+            HIP_TRY(hipMalloc(&na, cap));
+            HIP_TRY(hipMemcpy(na, in.arena, in_tail_known,
+                              hipMemcpyDeviceToDevice));
+            hipFree(in.arena);
+            in.arena = na;
+            in.arena_cap = cap;
+        }
+        return RW_OK;
+    }
+
+    // room for `add` more entries: the bound may pass 0.7 of the capacity
+    // only after an exact count, and past half the table doubles (rehash)
+    int intern_table_ensure(uint64_t add) {
+        uint64_t tcap = (uint64_t)in.cap_mask + 1;
+        if ((in_n_known + in_n_pending + add) * 10 <= tcap * 7) return RW_OK;
+        int rc = intern_sync_counts();
+        if (rc != RW_OK) return rc;
+        uint64_t ncap = tcap;
+        while ((in_n_known + add) * 2 > ncap) ncap <<= 1;
+        if (ncap > (1ull << 31))
+            FAIL(RW_E_INVAL, "varchar group-key intern table > 2^31 slots");
+        if (ncap != tcap) {
+            uint64_t* ns = nullptr;
+            HIP_TRY(hipMalloc(&ns, ncap * 8));
+            HIP_TRY(hipMemsetAsync(ns, 0, ncap * 8, stream));
+            agg_intern_rehash_kernel<<<grid_for((uint32_t)tcap), 256, 0,
+                                       stream>>>(in.slots, (uint32_t)tcap, ns,
+                                                 (uint32_t)(ncap - 1),
+                                                 in.arena);
+            HIP_TRY(hipStreamSynchronize(stream));
+            hipFree(in.slots);
+            in.slots = ns;
+            in.cap_mask = (uint32_t)(ncap - 1);
+        }
+        return RW_OK;
+    }
+
+    // size everything one pre-pass over `cells` (row, varchar column) cells
+    // holding `bytes` string bytes needs; the stream is idle between pushes
+    // (push_chunk ends synchronised), so scratch is reallocated freely
+    int intern_prepare(uint64_t cells, uint64_t bytes) {
+        int rc = intern_init();
+        if (rc != RW_OK) return rc;
+        if (bytes >= rwvarlen::PROV_BIT || cells > UINT32_MAX)
+            FAIL(RW_E_INVAL, "varchar group-key batch too large");
+        if (in_stg_cap < bytes + 1) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (in_stg) hipFree(in_stg);
+            in_stg = nullptr;
+            in_stg_cap = 0;
+            uint64_t cap = 1ull << 16;
+            while (cap < bytes + 1) cap <<= 1;
+            HIP_TRY(hipMalloc(&in_stg, cap));
+            in_stg_cap = cap;
+        }
+        in.stg = in_stg;
+        if (in_row_cap < cells) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (in.rowslot) hipFree(in.rowslot);
+            if (in.winners) hipFree(in.winners);
+            in.rowslot = in.winners = nullptr;
+            in_row_cap = 0;
+            uint64_t cap = 4096;
+            while (cap < cells) cap <<= 1;
+            HIP_TRY(hipMalloc(&in.rowslot, cap * 4));
+            HIP_TRY(hipMalloc(&in.winners, cap * 4));
+            in_row_cap = (uint32_t)(cap > UINT32_MAX ? UINT32_MAX : cap);
+        }
+        rc = intern_arena_ensure(bytes);
+        if (rc != RW_OK) return rc;
+        rc = intern_table_ensure(cells);
+        if (rc != RW_OK) return rc;
+        // only now: either ensure may have taken exact counts, which zeroes
+        // the pending bounds, and this batch's launches come after both
+        in_tail_pending += bytes;
+        in_n_pending += cells;
+        return RW_OK;
+    }
+
+    // the pre-pass: lookup -> commit -> resolve, launch-separated
+    int intern_run(const InternCols& c) {
+        uint32_t cells = c.n_rows * c.nv;
+        if (!cells) return RW_OK;
+        HIP_TRY(hipMemsetAsync(in.ctr, 0, 4, stream)); // winners of this push
+        int grid = grid_for(cells);
+        if (in_timing && !in_ev[0])
+            for (auto& ev : in_ev) HIP_TRY(hipEventCreate(&ev));
+        if (in_timing) HIP_TRY(hipEventRecord(in_ev[0], stream));
+        agg_intern_lookup_kernel<<<grid, 256, 0, stream>>>(in, c);
+        if (in_timing) HIP_TRY(hipEventRecord(in_ev[1], stream));
+        agg_intern_commit_kernel<<<grid < 256 ? grid : 256, 256, 0, stream>>>(in);
+        if (in_timing) HIP_TRY(hipEventRecord(in_ev[2], stream));
+        agg_intern_resolve_kernel<<<grid, 256, 0, stream>>>(in, c);
+        if (in_timing) {
+            HIP_TRY(hipEventRecord(in_ev[3], stream));
+            in_ev_pending = true;
+        }
+        return RW_OK;
+    }
+
+    // RW_AGG_INTERN_TIMING=1 (read at create; tests/bench_varchar_agg.py):
+    // an event around each pre-pass kernel, read back where the push has
+    // synchronised anyway
+    bool in_timing = false, in_ev_pending = false;
+    hipEvent_t in_ev[4] = {};
+    double in_ms[3] = {0, 0, 0};
+    uint64_t in_timed_launches = 0;
+    int intern_harvest() {
+        if (!in_ev_pending) return RW_OK;
+        in_ev_pending = false;
+        HIP_TRY(hipEventSynchronize(in_ev[3]));
+        for (int k = 0; k < 3; k++) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, in_ev[k], in_ev[k + 1]));
+            in_ms[k] += ms;
+        }
+        in_timed_launches++;
+        return RW_OK;
+    }
+
+    // validate a chunk's varchar key columns; reads offsets only
+    int intern_validate(const RwChunk* c, uint64_t* total_bytes) {
+        uint64_t total = 0;
+        for (int j = 0; j < nv; j++) {
+            uint32_t ci = group_key[vpos[j]];
+            if (c->cols[ci].type != RW_T_VARCHAR)
+                FAIL(RW_E_INVAL, "column %u: expected a varchar column", ci);
+            auto* vd = (const RwVarlenData*)c->cols[ci].data;
+            const char* why = vd ? rwvarlen::validate_offsets(vd->offsets,
+                                                              c->n_rows)
+                                 : "data is NULL";
+            if (why) FAIL(RW_E_INVAL, "varchar column %u: %s", ci, why);
+            if (c->n_rows && vd->offsets[c->n_rows] && !vd->bytes)
+                FAIL(RW_E_INVAL, "varchar column %u: bytes is NULL", ci);
+            total += c->n_rows ? vd->offsets[c->n_rows] : 0;
+        }
+        *total_bytes = total;
+        return RW_OK;
+    }
+
+    // flush / clean: fetch the strings of n rows of key words, key position
+    // k of row i at base[i * stride + k], into vk_offs / vk_bytes. A NULL
+    // key's word is 0, so it yields length 0 without a null mask.
+    int fetch_key_strings(const uint64_t* base, uint32_t stride, uint32_t n) {
+        for (int j = 0; j < nv; j++) {
+            int k = vpos[j];
+            VarlenView v{base + k, stride, nullptr, nullptr, 0};
+            int rc = vf.fetch(v, in.arena, n, vk_offs[k], vk_bytes[k],
+                              in_timing, stream);
+            if (rc != RW_OK) return rc;
+        }
+        return RW_OK;
+    }
+
+    // one key datum of emitted / spilled row r into a memcomparable key or
+    // a value row
+    void encode_key_datum(std::vector<uint8_t>& buf, bool memcmp_key, int k,
+                          uint32_t r, bool null, long long word) const {
+        if ((vc_mask >> k) & 1) {
+            uint64_t o = vk_offs[k][r];
+            uint32_t len = (uint32_t)(vk_offs[k][r + 1] - o);
+            const uint8_t* s = vk_bytes[k].data() + o;
+            if (memcmp_key) rwcodec::memcmp_encode_str(buf, null, s, len);
+            else rwcodec::value_encode_str(buf, null, s, len);
+            return;
+        }
+        rwcodec::DatumC d{null, word, 0};
+        if (memcmp_key) rwcodec::memcmp_encode_datum(buf, out_types[k], d, {});
+        else rwcodec::value_encode_datum(buf, out_types[k], d);
     }
 
     // Tiles (256 rows) per wave for the dense kernel's span mapping: the
@@ -2310,6 +2757,7 @@ struct HashAgg {
         desc = *d;
         eowc = d->emit_on_window_close != 0;
         if (const char* e = getenv("RW_AGG_FUSE_FLUSH")) fuse_env = *e == '1';
+        if (const char* e = getenv("RW_AGG_INTERN_TIMING")) in_timing = *e == '1';
         input_types.assign(d->input_types, d->input_types + d->n_input_cols);
         group_key.assign(d->group_key_indices, d->group_key_indices + d->n_group_key);
         calls.assign(d->calls, d->calls + d->n_calls);
@@ -2317,10 +2765,28 @@ struct HashAgg {
         n_calls = (int)calls.size();
         if (KW < 1 || KW > MAX_KW) FAIL(RW_E_INVAL, "group key width %d unsupported (1..%d)", KW, MAX_KW);
         if (n_calls < 1 || n_calls > 4) FAIL(RW_E_INVAL, "n_calls %d unsupported (1..4 in round-1 kernels)", n_calls);
-        for (auto k : group_key) {
-            uint8_t ty = input_types[k];
-            if (ty != RW_T_I64 && ty != RW_T_TS)
-                FAIL(RW_E_INVAL, "group key type %d unsupported on GPU (i64/ts only)", ty);
+        for (int i = 0; i < KW; i++) {
+            uint8_t ty = input_types[group_key[i]];
+            if (ty == RW_T_VARCHAR) {
+                vc_mask |= 1u << i;
+                vpos[nv++] = i;
+            } else if (ty != RW_T_I64 && ty != RW_T_TS) {
+                FAIL(RW_E_INVAL, "group key type %d unsupported on GPU (i64/ts/varchar only)", ty);
+            }
+        }
+        if (has_vc()) {
+            // scope of varchar group keys (rw_stream.h)
+            if (eowc)
+                FAIL(RW_E_INVAL, "varchar group key + emit_on_window_close unsupported");
+            for (auto& c : calls) {
+                if (c.distinct)
+                    FAIL(RW_E_INVAL, "varchar group key + DISTINCT call unsupported");
+                if ((c.kind == RW_AGG_MIN || c.kind == RW_AGG_MAX) &&
+                    !d->append_only)
+                    FAIL(RW_E_INVAL,
+                         "varchar group key + materialized-input min/max "
+                         "unsupported (append-only min/max is)");
+            }
         }
         stream_key.assign(d->stream_key, d->stream_key + d->n_stream_key);
         for (auto& c : calls) {
@@ -2502,13 +2968,49 @@ struct HashAgg {
     int upload(const RwChunk* c, AggBatch* out, bool use_stage) {
         uint32_t n = c->n_rows;
         AggBatch b{};
+        // varchar key columns: validate every offsets array BEFORE any copy
+        // or state change, then size the interning state for this chunk
+        uint64_t vbytes_total = 0;
+        if (has_vc()) {
+            if (!use_stage)
+                FAIL(RW_E_INVAL, "varchar group keys: device-resident batches unsupported");
+            int rc = intern_validate(c, &vbytes_total);
+            if (rc != RW_OK) return rc;
+            rc = intern_prepare((uint64_t)n * nv, vbytes_total);
+            if (rc != RW_OK) return rc;
+        }
         if (use_stage) {
             int rc = ensure_stage(n);
             if (rc != RW_OK) return rc;
             b = stage;
         }
+        uint64_t vbase = 0; // staging offset of the next varchar column
         auto upcol = [&](int bi, uint32_t col_idx) -> int {
             const RwColumn& col = c->cols[col_idx];
+            if (bi < KW && ((vc_mask >> bi) & 1)) {
+                // bytes go to the STAGING buffer (not the arena); the words
+                // staged where i64 values go are provisional
+                auto* vd = (const RwVarlenData*)col.data;
+                uint64_t total = n ? vd->offsets[n] : 0;
+                if (total)
+                    HIP_TRY(hipMemcpyAsync(in_stg + vbase, vd->bytes, total,
+                                           hipMemcpyHostToDevice, stream));
+                auto& w = vwords[bi];
+                w.resize(n);
+                for (uint32_t r = 0; r < n; r++)
+                    w[r] = col.valid[r]
+                               ? (int64_t)rwvarlen::pack(
+                                     rwvarlen::PROV_BIT |
+                                         (vbase + vd->offsets[r]),
+                                     vd->offsets[r + 1] - vd->offsets[r])
+                               : 0;
+                vbase += total;
+                HIP_TRY(hipMemcpyAsync(b.col_vals[bi], w.data(), (size_t)n * 8,
+                                       hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(b.col_valid[bi], col.valid, n,
+                                       hipMemcpyHostToDevice, stream));
+                return RW_OK;
+            }
             size_t w = 8;
             if (col.type == RW_T_DECIMAL) w = 16; // 2 words/row
             else if (col.type != RW_T_I64 && col.type != RW_T_TS)
@@ -2891,6 +3393,18 @@ struct HashAgg {
         AggBatch b;
         int rc = upload(c, &b, true);
         if (rc != RW_OK) return rc;
+        if (has_vc()) {
+            // make the batch's varchar key words canonical;
+            // from here on the batch is an i64 batch
+            InternCols ic{};
+            for (int j = 0; j < nv; j++) ic.words[j] = b.col_vals[vpos[j]];
+            ic.vis = b.vis;
+            ic.n_rows = b.n_rows;
+            ic.nv = (uint32_t)nv;
+            ic.stride = 1;
+            rc = intern_run(ic);
+            if (rc != RW_OK) return rc;
+        }
         if (!distinct_slots.empty()) {
             rc = ensure_dedup(c->n_rows);
             if (rc != RW_OK) return rc;
@@ -2907,6 +3421,7 @@ struct HashAgg {
         rc = apply(b, true, minput_conflict_segments(c));
         if (rc != RW_OK) return rc;
         HIP_TRY(hipStreamSynchronize(stream)); // staging buffer reuse
+        if (in_ev_pending && intern_harvest() != RW_OK) return RW_E_INTERNAL;
         return check_overflow();
     }
 
@@ -2919,6 +3434,8 @@ struct HashAgg {
         if (ctr[2] == 2) FAIL(RW_E_INTERNAL, "agg output buffer overflow");
         if (ctr[2] == 3) FAIL(RW_E_INTERNAL, "agg minput row store full");
         if (ctr[2] == 4) FAIL(RW_E_INTERNAL, "agg distinct dedup table full");
+        if (ctr[2] == AGG_ERR_INTERN)
+            FAIL(RW_E_INTERNAL, "agg varchar group-key intern table or arena full");
         if (ctr[2] == 5)
             FAIL(RW_E_OVERFLOW,
                  "decimal sum outside the exact 96-bit domain (the "
@@ -3018,6 +3535,10 @@ struct HashAgg {
         uint32_t n_dirty = 0;
         int rcp = presize_flush_out(&n_dirty);
         if (rcp != RW_OK) return rcp;
+        if (has_vc()) { // the stream is drained: exact tail / entry count
+            rcp = intern_sync_counts();
+            if (rcp != RW_OK) return rcp;
+        }
         if (eowc) {
             // EOWC barrier (hash_agg.rs:429-474): nothing is EMITTED until a
             // watermark closes windows, but the dirty groups' current states
@@ -3125,6 +3646,11 @@ struct HashAgg {
             std::vector<uint8_t> nulls((size_t)n_out * out_width);
             std::vector<uint8_t> ops(n_out);
             std::vector<long long> vals2;
+            if (has_vc()) { // strings of the emitted varchar key columns
+                int rcv = fetch_key_strings((const uint64_t*)t.out_vals,
+                                            (uint32_t)out_width, n_out);
+                if (rcv != RW_OK) return rcv;
+            }
             HIP_TRY(hipMemcpy(vals.data(), t.out_vals, vals.size() * 8,
                               hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(nulls.data(), t.out_nulls, nulls.size(),
@@ -3186,17 +3712,15 @@ struct HashAgg {
             uint8_t put = op != RW_OP_DELETE;
             spill.push_back(put);
             std::vector<uint8_t> k, v;
-            for (int i = 0; i < KW; i++) {
-                rwcodec::DatumC d{nulls[(size_t)r * out_width + i] != 0,
-                                  vals[(size_t)r * out_width + i], 0};
-                rwcodec::memcmp_encode_datum(k, out_types[i], d, {});
-            }
+            for (int i = 0; i < KW; i++)
+                encode_key_datum(k, true, i, r,
+                                 nulls[(size_t)r * out_width + i] != 0,
+                                 vals[(size_t)r * out_width + i]);
             if (put) {
-                for (int i = 0; i < KW; i++) {
-                    rwcodec::DatumC d{nulls[(size_t)r * out_width + i] != 0,
-                                      vals[(size_t)r * out_width + i], 0};
-                    rwcodec::value_encode_datum(v, out_types[i], d);
-                }
+                for (int i = 0; i < KW; i++)
+                    encode_key_datum(v, false, i, r,
+                                     nulls[(size_t)r * out_width + i] != 0,
+                                     vals[(size_t)r * out_width + i]);
                 for (int ci = 0; ci < n_calls; ci++) {
                     if (call_minput[ci]) {
                         rwcodec::value_encode_datum(v, calls[ci].ret_type,
@@ -3805,6 +4329,24 @@ struct HashAgg {
                 cols[ci].data = data;
                 continue;
             }
+            if (ci < KW && ((vc_mask >> ci) & 1)) {
+                // a varchar key column: offsets rebased to this chunk's
+                // first row; NULL rows have zero length
+                const auto& so = vk_offs[ci];
+                uint64_t base = so[start], total = so[start + n] - base;
+                auto* offs = new uint32_t[(size_t)n + 1];
+                auto* bytes = new uint8_t[total ? total : 1];
+                auto* valid = new uint8_t[n];
+                for (uint32_t r = 0; r <= n; r++)
+                    offs[r] = (uint32_t)(so[start + r] - base);
+                if (total) memcpy(bytes, vk_bytes[ci].data() + base, total);
+                for (uint32_t r = 0; r < n; r++)
+                    valid[r] = !nulls[(size_t)(start + r) * out_width + ci];
+                cols[ci].type = ty;
+                cols[ci].valid = valid;
+                cols[ci].data = new RwVarlenData{offs, bytes};
+                continue;
+            }
             auto* data = new int64_t[n];
             auto* valid = new uint8_t[n];
             for (uint32_t r = 0; r < n; r++) {
@@ -3832,6 +4374,17 @@ struct HashAgg {
 
     ~HashAgg() {
         free_stage();
+        if (in_ready) {
+            hipFree(in.arena);
+            hipFree(in.slots);
+            hipFree(in.tail);
+            hipFree(in.ctr);
+        }
+        if (in_stg) hipFree(in_stg);
+        if (in.rowslot) hipFree(in.rowslot);
+        if (in.winners) hipFree(in.winners);
+        for (auto ev : in_ev)
+            if (ev) hipEventDestroy(ev);
         if (ecap) {
             for (int i = 0; i < n_batch_slots(); i++) {
                 hipFree(ebuf.col_vals[i]);
@@ -3978,9 +4531,58 @@ int rw_hash_agg_push_chunk(void* h, const RwChunk* c) {
 }
 int rw_hash_agg_flush(void* h, uint64_t epoch) { return ((HashAgg*)h)->flush(epoch); }
 
+// the epoch-staging, device-batch and device-hop entry points move 8-byte
+// words with no arena behind them (rw_stream.h: varchar group keys)
+#define AGG_NO_VARCHAR(agg, what)                                         \
+    do {                                                                  \
+        if ((agg)->has_vc())                                              \
+            FAIL(RW_E_INVAL, what " is not supported on a HashAgg with "  \
+                                  "varchar group keys");                  \
+    } while (0)
+
+int rw_hash_agg_varlen_reserve(void* h, uint64_t arena_bytes,
+                               uint64_t n_strings) {
+    auto* agg = (HashAgg*)h;
+    if (!agg->has_vc())
+        FAIL(RW_E_INVAL, "rw_hash_agg_varlen_reserve: no varchar group key");
+    if (agg->in_ready)
+        FAIL(RW_E_INVAL, "rw_hash_agg_varlen_reserve: call before the first "
+                         "push or restore");
+    if (arena_bytes > rwvarlen::AGG_ARENA_MAX || n_strings > (1ull << 30))
+        FAIL(RW_E_INVAL, "rw_hash_agg_varlen_reserve: size out of range");
+    agg->in_reserve_arena = arena_bytes;
+    agg->in_reserve_strings = n_strings;
+    return RW_OK;
+}
+
+int rw_hash_agg_varlen_stats(void* h, uint64_t* arena_used,
+                             uint64_t* arena_cap, uint64_t* n_strings,
+                             uint64_t* table_cap) {
+    auto* agg = (HashAgg*)h;
+    int rc = agg->intern_sync_counts(); // exact values; no-op when unused
+    if (rc != RW_OK) return rc;
+    bool on = agg->in_ready;
+    if (arena_used) *arena_used = on ? agg->in_tail_known : 0;
+    if (arena_cap) *arena_cap = on ? agg->in.arena_cap : 0;
+    if (n_strings) *n_strings = on ? agg->in_n_known : 0;
+    if (table_cap) *table_cap = on ? (uint64_t)agg->in.cap_mask + 1 : 0;
+    return RW_OK;
+}
+
+int rw_hash_agg_varlen_intern_stats(void* h, double* kernel_ms,
+                                    double* fetch_ms, uint64_t* launches) {
+    auto* agg = (HashAgg*)h;
+    if (kernel_ms)
+        for (int k = 0; k < 3; k++) kernel_ms[k] = agg->in_ms[k];
+    if (fetch_ms) *fetch_ms = agg->vf.vemit_ms;
+    if (launches) *launches = agg->in_timed_launches;
+    return RW_OK;
+}
+
 // epoch-batched ingest mode (rw_stream.h): push_chunk stages, flush applies
 int rw_hash_agg_ingest_mode(void* h, int epoch_batched) {
     auto* agg = (HashAgg*)h;
+    if (epoch_batched) AGG_NO_VARCHAR(agg, "epoch-batched ingest");
     if (epoch_batched && agg->n_dec)
         FAIL(RW_E_INVAL, "epoch-batched ingest + decimal not yet supported");
     if (epoch_batched && (agg->n_minput > 0 || !agg->distinct_slots.empty()))
@@ -3999,6 +4601,11 @@ void rw_hash_agg_destroy(void* h) { delete (HashAgg*)h; }
 
 void* rw_agg_bench_preload(void* h, const RwChunk* c) {
     auto* agg = (HashAgg*)h;
+    if (agg->has_vc()) {
+        g_err = "rw_agg_bench_preload is not supported on a HashAgg with "
+                "varchar group keys";
+        return nullptr;
+    }
     auto* b = new AggBatch{};
     uint32_t n = c->n_rows;
     for (int i = 0; i < agg->n_batch_slots(); i++) {
@@ -4028,6 +4635,7 @@ void* rw_agg_bench_preload(void* h, const RwChunk* c) {
 
 int rw_agg_bench_apply(void* h, void* batch) {
     auto* agg = (HashAgg*)h;
+    AGG_NO_VARCHAR(agg, "rw_agg_bench_apply");
     return agg->apply(*(AggBatch*)batch, true);
 }
 
@@ -4042,6 +4650,7 @@ int rw_agg_apply_flush_launch(void* h, void* batch, uint32_t r0, uint32_t r1,
 int rw_agg_bench_run(void* h, void** batches, int n_batches, int steps,
                      int barrier_every, int step0) {
     auto* agg = (HashAgg*)h;
+    AGG_NO_VARCHAR(agg, "rw_agg_bench_run");
     for (int i = 0; i < steps; i++) {
         int rc = agg->apply(*(AggBatch*)batches[(step0 + i) % n_batches], true);
         if (rc != RW_OK) return rc;
@@ -4063,6 +4672,7 @@ int rw_agg_bench_run(void* h, void** batches, int n_batches, int steps,
 int rw_agg_bench_run_epochs(void* h, void* giant, uint64_t rows_per_step,
                             int n_slots, int steps, int barrier_every,
                             int step0) {
+    AGG_NO_VARCHAR((HashAgg*)h, "rw_agg_bench_run_epochs");
     if (barrier_every <= 0 || n_slots % barrier_every ||
         step0 % barrier_every)
         FAIL(RW_E_INVAL, "epoch run needs barrier_every | n_slots, aligned step0");
@@ -4116,6 +4726,7 @@ int rw_agg_apply_payload(void* h, const uint8_t* payload,
                          const uint64_t* block_rows, int n_blocks, int n_cols,
                          int dense) {
     auto* agg = (HashAgg*)h;
+    AGG_NO_VARCHAR(agg, "rw_agg_apply_payload");
     if (agg->n_dec)
         FAIL(RW_E_INVAL, "decimal columns not yet carried by the exchange");
     if (n_cols != agg->KW + agg->n_calls)
@@ -4181,6 +4792,7 @@ __global__ void agg_counters_reset_kernel(uint32_t* counters) {
 // for the downstream, as with rw_agg_flush_device.
 int rw_agg_flush_launch(void* h, uint64_t epoch) {
     auto* agg = (HashAgg*)h;
+    AGG_NO_VARCHAR(agg, "rw_agg_flush_launch");
     (void)epoch;
     agg->launch_flush(-1, true);
     return RW_OK;
@@ -4195,6 +4807,7 @@ int rw_agg_flush_launch(void* h, uint64_t epoch) {
 int rw_agg_apply_flush_launch(void* h, void* batch, uint32_t r0, uint32_t r1,
                               uint64_t epoch) {
     auto* agg = (HashAgg*)h;
+    AGG_NO_VARCHAR(agg, "rw_agg_apply_flush_launch");
     auto* b = (AggBatch*)batch;
     if (r0 > r1 || r1 > b->n_rows)
         FAIL(RW_E_INVAL, "apply range [%u, %u) outside the batch's %u rows", r0,
@@ -4320,6 +4933,9 @@ int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
     std::vector<uint8_t> vnulls((size_t)nc * n);
     std::vector<long long> vals2;
     if (agg->n_dec) vals2.assign((size_t)nc * n, 0);
+    // varchar group keys: the decoded strings are packed into one host
+    // buffer and take the same staging + intern path a pushed chunk does
+    std::vector<uint8_t> sbytes;
     uint32_t i = 0;
     for (auto& [kbytes, val] : merged) {
         (void)kbytes;
@@ -4327,6 +4943,24 @@ int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
         for (int c = 0; c < KW + nc; c++) {
             rwcodec::DatumC d;
             uint8_t ty = agg->out_types[c];
+            if (c < KW && ((agg->vc_mask >> c) & 1)) {
+                bool null = false;
+                const uint8_t* s = nullptr;
+                uint32_t slen = 0;
+                size_t gots = rwcodec::value_decode_str(
+                    val.data() + off, val.size() - off, &null, &s, &slen);
+                if (!gots || slen > rwvarlen::MAX_LEN)
+                    FAIL(RW_E_INVAL, "restore: bad varchar key datum");
+                off += gots;
+                keys[(size_t)i * KW + c] =
+                    null ? 0
+                         : (int64_t)rwvarlen::pack(
+                               rwvarlen::PROV_BIT | (uint64_t)sbytes.size(),
+                               slen);
+                knulls[i] |= (uint32_t)null << c;
+                if (!null) sbytes.insert(sbytes.end(), s, s + slen);
+                continue;
+            }
             size_t got = rwcodec::value_decode_datum(val.data() + off,
                                                      val.size() - off, ty, &d);
             if (!got) FAIL(RW_E_INVAL, "restore: bad state datum");
@@ -4364,6 +4998,33 @@ int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
         HIP_TRY(hipMalloc(&dvals2, vals2.size() * 8));
         HIP_TRY(hipMemcpy(dvals2, vals2.data(), vals2.size() * 8,
                           hipMemcpyHostToDevice));
+    }
+    if (agg->has_vc()) {
+        int rcv = agg->intern_prepare((uint64_t)n * agg->nv, sbytes.size());
+        if (rcv == RW_OK && !sbytes.empty() &&
+            hipMemcpy(agg->in_stg, sbytes.data(), sbytes.size(),
+                      hipMemcpyHostToDevice) != hipSuccess) {
+            g_err = "restore: staging copy failed";
+            rcv = RW_E_INTERNAL;
+        }
+        if (rcv == RW_OK) {
+            InternCols ic{};
+            for (int j = 0; j < agg->nv; j++)
+                ic.words[j] = dkeys + agg->vpos[j];
+            ic.vis = nullptr;
+            ic.n_rows = n;
+            ic.nv = (uint32_t)agg->nv;
+            ic.stride = (uint32_t)KW;
+            rcv = agg->intern_run(ic);
+        }
+        if (rcv != RW_OK) {
+            hipFree(dkeys);
+            hipFree(dknulls);
+            hipFree(dvals);
+            hipFree(dvnulls);
+            if (dvals2) hipFree(dvals2);
+            return rcv;
+        }
     }
     agg_restore_kernel<<<agg->grid_for(n), 256, 0, agg->stream>>>(
         agg->t, KW, nc, dkeys, dknulls, dvals, dvnulls, dvals2, n,
@@ -6215,18 +6876,8 @@ __global__ void join_vnode_scope_kernel(JoinSideDev sd, int KW,
 // retractions by string content, materialising strings for emit / drain,
 // and rebuilding the arena at compaction.
 
-// n reference words, word i at words[i * stride] (stride in 8-byte units:
-// 1 for a columnar block, row_stride / 8 for a column of packed records).
-// Optional masks yield the zero word (length 0): nulls[i] != 0 (the join
-// output block's NULL flags) and ops[i] == 0xFF for i < sparse_n (the inner
-// probe's pre-assigned sparse region — those slots hold unwritten words).
-struct VarlenView {
-    const uint64_t* words;
-    uint32_t stride;
-    const uint8_t* nulls;
-    const uint8_t* ops;
-    uint32_t sparse_n;
-};
+// (VarlenView and the VarlenFetch materialiser both executors share are
+// declared ahead of HashAgg.)
 
 __device__ __forceinline__ uint64_t varlen_view_word(const VarlenView& v,
                                                      uint32_t i) {
@@ -6439,6 +7090,107 @@ __global__ void varlen_rewrite_kernel(JoinSideDev sd, int col, uint32_t n,
                               new_base + offs[i],
                               rwvarlen::word_len((uint64_t)hv[col]))
                         : 0;
+    }
+}
+
+int VarlenFetch::ensure_vscratch(uint32_t n) {
+    if (d_vcap >= n + 1) return RW_OK;
+    if (d_vlens) hipFree(d_vlens);
+    if (d_voffs) hipFree(d_voffs);
+    d_vlens = d_voffs = nullptr;
+    d_vcap = 0;
+    uint32_t cap = 4096;
+    while (cap < n + 1) cap <<= 1;
+    HIP_TRY(hipMalloc(&d_vlens, (size_t)cap * 8));
+    HIP_TRY(hipMalloc(&d_voffs, (size_t)cap * 8));
+    d_vcap = cap;
+    return RW_OK;
+}
+
+// Materialise the strings a view's words reference into ONE packed
+// host byte buffer: length kernel -> exclusive scan -> copy kernel ->
+// D2H. offs gets n + 1 entries (offs[n] = total bytes).
+int VarlenFetch::fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
+                       std::vector<uint64_t>& offs,
+                       std::vector<uint8_t>& bytes, bool timed,
+                       hipStream_t stream) {
+    offs.assign((size_t)n + 1, 0);
+    bytes.clear();
+    if (!n) return RW_OK;
+    int rc = ensure_vscratch(n);
+    if (rc != RW_OK) return rc;
+    if (timed && !vev0) {
+        HIP_TRY(hipEventCreate(&vev0));
+        HIP_TRY(hipEventCreate(&vev1));
+        HIP_TRY(hipEventCreate(&vev2));
+    }
+    if (timed) HIP_TRY(hipEventRecord(vev0, stream));
+    uint32_t blocks = (n + 1 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    varlen_len_kernel<<<blocks, 256, 0, stream>>>(v, n, d_vlens);
+    size_t tmp = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, d_vlens, d_voffs,
+                                    (uint64_t)0, (size_t)n + 1,
+                                    rocprim::plus<uint64_t>(), stream));
+    if (tmp > d_scan_tmp_cap) {
+        if (d_scan_tmp) hipFree(d_scan_tmp);
+        d_scan_tmp = nullptr;
+        d_scan_tmp_cap = 0;
+        HIP_TRY(hipMalloc(&d_scan_tmp, tmp));
+        d_scan_tmp_cap = tmp;
+    }
+    HIP_TRY(rocprim::exclusive_scan(d_scan_tmp, tmp, d_vlens, d_voffs,
+                                    (uint64_t)0, (size_t)n + 1,
+                                    rocprim::plus<uint64_t>(), stream));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_voffs + n, 8, hipMemcpyDeviceToHost,
+                           stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (total) {
+        uint64_t padded = total + VARLEN_COPY_PAD; // whole copy units
+        if (d_vbytes_cap < padded) {
+            if (d_vbytes) hipFree(d_vbytes);
+            d_vbytes = nullptr;
+            d_vbytes_cap = 0;
+            uint64_t cap = 1ull << 16;
+            while (cap < padded) cap <<= 1;
+            HIP_TRY(hipMalloc(&d_vbytes, cap));
+            d_vbytes_cap = cap;
+        }
+        if (timed) HIP_TRY(hipEventRecord(vev2, stream));
+        varlen_copy_launch(v, arena, d_voffs, n, total, d_vbytes, stream);
+    }
+    if (timed) {
+        HIP_TRY(hipEventRecord(vev1, stream));
+        HIP_TRY(hipEventSynchronize(vev1));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, vev0, vev1));
+        vemit_ms += ms;
+        if (total) {
+            HIP_TRY(hipEventElapsedTime(&ms, vev2, vev1));
+            vcopy_ms += ms;
+        }
+        vemit_bytes += total;
+        vemit_launches++;
+    }
+    HIP_TRY(hipMemcpy(offs.data(), d_voffs, ((size_t)n + 1) * 8,
+                      hipMemcpyDeviceToHost));
+    bytes.resize(total);
+    if (total)
+        HIP_TRY(hipMemcpy(bytes.data(), d_vbytes, total,
+                          hipMemcpyDeviceToHost));
+    return RW_OK;
+}
+
+VarlenFetch::~VarlenFetch() {
+    if (d_vlens) hipFree(d_vlens);
+    if (d_voffs) hipFree(d_voffs);
+    if (d_vbytes) hipFree(d_vbytes);
+    if (d_scan_tmp) hipFree(d_scan_tmp);
+    if (vev0) {
+        hipEventDestroy(vev0);
+        hipEventDestroy(vev1);
+        if (vev2) hipEventDestroy(vev2);
     }
 }
 
@@ -6711,17 +7463,8 @@ struct HashJoin {
     // host staging of a batch's reference words; lives until the next
     // upload so the async H2D copy never outlives its source
     std::vector<int64_t> vwords[2][MAX_COLS];
-    // emit-path materialisation scratch + stats
-    uint64_t* d_vlens = nullptr;
-    uint64_t* d_voffs = nullptr;
-    uint32_t d_vcap = 0;
-    uint8_t* d_vbytes = nullptr;
-    uint64_t d_vbytes_cap = 0;
-    void* d_scan_tmp = nullptr;
-    size_t d_scan_tmp_cap = 0;
-    hipEvent_t vev0 = nullptr, vev1 = nullptr, vev2 = nullptr;
-    double vemit_ms = 0, vcopy_ms = 0; // whole materialise / copy kernel
-    uint64_t vemit_bytes = 0, vemit_launches = 0;
+    // emit-path materialisation scratch + stats (shared with HashAgg)
+    VarlenFetch vf;
 
     bool has_varchar() const { return (m.vc_mask[0] | m.vc_mask[1]) != 0; }
 
@@ -6750,92 +7493,11 @@ struct HashJoin {
         return RW_OK;
     }
 
-    int ensure_vscratch(uint32_t n) {
-        if (d_vcap >= n + 1) return RW_OK;
-        if (d_vlens) hipFree(d_vlens);
-        if (d_voffs) hipFree(d_voffs);
-        d_vlens = d_voffs = nullptr;
-        d_vcap = 0;
-        uint32_t cap = 4096;
-        while (cap < n + 1) cap <<= 1;
-        HIP_TRY(hipMalloc(&d_vlens, (size_t)cap * 8));
-        HIP_TRY(hipMalloc(&d_voffs, (size_t)cap * 8));
-        d_vcap = cap;
-        return RW_OK;
-    }
-
-    // Materialise the strings a view's words reference into ONE packed
-    // host byte buffer: length kernel -> exclusive scan -> copy kernel ->
-    // D2H. offs gets n + 1 entries (offs[n] = total bytes).
+    int ensure_vscratch(uint32_t n) { return vf.ensure_vscratch(n); }
     int varlen_fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
                      std::vector<uint64_t>& offs, std::vector<uint8_t>& bytes,
                      bool timed) {
-        offs.assign((size_t)n + 1, 0);
-        bytes.clear();
-        if (!n) return RW_OK;
-        int rc = ensure_vscratch(n);
-        if (rc != RW_OK) return rc;
-        if (timed && !vev0) {
-            HIP_TRY(hipEventCreate(&vev0));
-            HIP_TRY(hipEventCreate(&vev1));
-            HIP_TRY(hipEventCreate(&vev2));
-        }
-        if (timed) HIP_TRY(hipEventRecord(vev0, stream));
-        uint32_t blocks = (n + 1 + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        varlen_len_kernel<<<blocks, 256, 0, stream>>>(v, n, d_vlens);
-        size_t tmp = 0;
-        HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, d_vlens, d_voffs,
-                                        (uint64_t)0, (size_t)n + 1,
-                                        rocprim::plus<uint64_t>(), stream));
-        if (tmp > d_scan_tmp_cap) {
-            if (d_scan_tmp) hipFree(d_scan_tmp);
-            d_scan_tmp = nullptr;
-            d_scan_tmp_cap = 0;
-            HIP_TRY(hipMalloc(&d_scan_tmp, tmp));
-            d_scan_tmp_cap = tmp;
-        }
-        HIP_TRY(rocprim::exclusive_scan(d_scan_tmp, tmp, d_vlens, d_voffs,
-                                        (uint64_t)0, (size_t)n + 1,
-                                        rocprim::plus<uint64_t>(), stream));
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&total, d_voffs + n, 8, hipMemcpyDeviceToHost,
-                               stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (total) {
-            uint64_t padded = total + VARLEN_COPY_PAD; // whole copy units
-            if (d_vbytes_cap < padded) {
-                if (d_vbytes) hipFree(d_vbytes);
-                d_vbytes = nullptr;
-                d_vbytes_cap = 0;
-                uint64_t cap = 1ull << 16;
-                while (cap < padded) cap <<= 1;
-                HIP_TRY(hipMalloc(&d_vbytes, cap));
-                d_vbytes_cap = cap;
-            }
-            if (timed) HIP_TRY(hipEventRecord(vev2, stream));
-            varlen_copy_launch(v, arena, d_voffs, n, total, d_vbytes, stream);
-        }
-        if (timed) {
-            HIP_TRY(hipEventRecord(vev1, stream));
-            HIP_TRY(hipEventSynchronize(vev1));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, vev0, vev1));
-            vemit_ms += ms;
-            if (total) {
-                HIP_TRY(hipEventElapsedTime(&ms, vev2, vev1));
-                vcopy_ms += ms;
-            }
-            vemit_bytes += total;
-            vemit_launches++;
-        }
-        HIP_TRY(hipMemcpy(offs.data(), d_voffs, ((size_t)n + 1) * 8,
-                          hipMemcpyDeviceToHost));
-        bytes.resize(total);
-        if (total)
-            HIP_TRY(hipMemcpy(bytes.data(), d_vbytes, total,
-                              hipMemcpyDeviceToHost));
-        return RW_OK;
+        return vf.fetch(v, arena, n, offs, bytes, timed, stream);
     }
 
     int upload(int s, const RwChunk* c, JoinBatchDev* bout) {
@@ -7622,15 +8284,6 @@ struct HashJoin {
             hipFree(d_emit_count);
         }
         if (d_vis_scratch) hipFree(d_vis_scratch);
-        if (d_vlens) hipFree(d_vlens);
-        if (d_voffs) hipFree(d_voffs);
-        if (d_vbytes) hipFree(d_vbytes);
-        if (d_scan_tmp) hipFree(d_scan_tmp);
-        if (vev0) {
-            hipEventDestroy(vev0);
-            hipEventDestroy(vev1);
-            if (vev2) hipEventDestroy(vev2);
-        }
         for (int s = 0; s < 2; s++) {
             if (compact_scratch[s]) hipFree(compact_scratch[s]);
             if (side[s].arena) hipFree(side[s].arena);
@@ -7732,10 +8385,10 @@ int rw_hash_join_varlen_stats(void* h, int side, uint64_t* used,
 int rw_hash_join_varlen_emit_stats(void* h, double* ms, double* copy_ms,
                                    uint64_t* bytes, uint64_t* launches) {
     auto* j = (HashJoin*)h;
-    if (ms) *ms = j->vemit_ms;
-    if (copy_ms) *copy_ms = j->vcopy_ms;
-    if (bytes) *bytes = j->vemit_bytes;
-    if (launches) *launches = j->vemit_launches;
+    if (ms) *ms = j->vf.vemit_ms;
+    if (copy_ms) *copy_ms = j->vf.vcopy_ms;
+    if (bytes) *bytes = j->vf.vemit_bytes;
+    if (launches) *launches = j->vf.vemit_launches;
     return RW_OK;
 }
 
@@ -7750,6 +8403,8 @@ int rw_hash_join_watermark(void* h, int side, uint32_t col_idx, int64_t val,
 int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
     auto* agg = (HashAgg*)h;
     if (group_key_pos >= (uint32_t)agg->KW) FAIL(RW_E_INVAL, "bad group key pos");
+    if ((agg->vc_mask >> group_key_pos) & 1)
+        FAIL(RW_E_INVAL, "watermark on a varchar group key unsupported");
     if (agg->eowc) {
         // EOWC: buffer the window watermark; windows close at the next
         // barrier (hash_agg.rs:657-700)
@@ -7782,9 +8437,17 @@ int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
         if (rcs == RW_OK && n)
             hipMemcpy(recs.data(), crecs, (size_t)n * sizeof(DedupDirtyRec),
                       hipMemcpyDeviceToHost);
+        // varchar key columns: the captured words' strings, for the DELETE
+        // frames' memcomparable keys
+        static_assert(sizeof(DedupDirtyRec) % 8 == 0, "word-strided view");
+        int rcv = RW_OK;
+        if (rcs == RW_OK && n && agg->has_vc())
+            rcv = agg->fetch_key_strings((const uint64_t*)crecs,
+                                         sizeof(DedupDirtyRec) / 8, n);
         hipFree(crecs);
         hipFree(cmeta);
         if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "agg clean sync failed");
+        if (rcv != RW_OK) return rcv;
         auto put32 = [&](uint32_t x) {
             for (int b = 0; b < 4; b++)
                 agg->spill.push_back((uint8_t)(x >> (8 * b)));
@@ -7792,11 +8455,10 @@ int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
         for (uint32_t i = 0; i < n; i++) {
             agg->spill.push_back(0); // DELETE
             std::vector<uint8_t> k;
-            for (int w = 0; w < agg->KW; w++) {
-                rwcodec::DatumC d{((recs[i].nulls >> w) & 1) != 0,
-                                  recs[i].key[w], 0};
-                rwcodec::memcmp_encode_datum(k, agg->out_types[w], d, {});
-            }
+            for (int w = 0; w < agg->KW; w++)
+                agg->encode_key_datum(k, true, w, i,
+                                      ((recs[i].nulls >> w) & 1) != 0,
+                                      recs[i].key[w]);
             put32((uint32_t)k.size());
             agg->spill.insert(agg->spill.end(), k.begin(), k.end());
             put32(0);
@@ -7821,6 +8483,7 @@ int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
 int rw_hash_agg_update_vnode_bitmap(void* h, const uint8_t* bitmap,
                                     uint32_t vnode_count) {
     auto* agg = (HashAgg*)h;
+    AGG_NO_VARCHAR(agg, "rw_hash_agg_update_vnode_bitmap");
     if (!vnode_count || vnode_count % 8 || vnode_count > 4096)
         FAIL(RW_E_INVAL, "vnode_count");
     if (ensure_crc_table() != RW_OK) FAIL(RW_E_INTERNAL, "crc table");
@@ -8014,6 +8677,7 @@ int rw_join_apply_aggout(void* join_h, void* agg_h, int side,
     auto* j = (HashJoin*)join_h;
     auto* agg = (HashAgg*)agg_h;
     JOIN_NO_VARCHAR(j, "rw_join_apply_aggout");
+    AGG_NO_VARCHAR(agg, "rw_join_apply_aggout");
     if (side != 0 && side != 1) FAIL(RW_E_INVAL, "bad side");
     if (n_map != j->m.n_cols[side])
         FAIL(RW_E_INVAL, "col_map size %d != side cols %d", n_map,
@@ -8085,6 +8749,7 @@ int rw_agg_apply_joinout(void* agg_h, void* join_h) {
     auto* agg = (HashAgg*)agg_h;
     auto* j = (HashJoin*)join_h;
     JOIN_NO_VARCHAR(j, "rw_agg_apply_joinout");
+    AGG_NO_VARCHAR(agg, "rw_agg_apply_joinout");
     if (agg->n_dec)
         FAIL(RW_E_INVAL, "decimal columns not yet in the join output block");
     if (hipStreamSynchronize(j->stream) != hipSuccess)
@@ -8168,6 +8833,7 @@ int rw_q7pipe_bench_run(void* agg_h, void* join_h, void** agg_batches,
     auto* agg = (HashAgg*)agg_h;
     auto* j = (HashJoin*)join_h;
     JOIN_NO_VARCHAR(j, "rw_q7pipe_bench_run");
+    AGG_NO_VARCHAR(agg, "rw_q7pipe_bench_run");
     // Long-run state maintenance: the agg change stream retires a right-
     // side record per replaced window max (U- then U+), so dead records
     // accumulate and lengthen the probe walks. Every RW_Q7PIPE_COMPACT
@@ -8449,32 +9115,32 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
             uint32_t blocks = (n_alive + 1 + 255) / 256;
             if (blocks > 4096) blocks = 4096;
             varlen_len_kernel<<<blocks, 256, 0, j->stream>>>(v, n_alive,
-                                                             j->d_vlens);
+                                                             j->vf.d_vlens);
             size_t tmp = 0;
-            if (rocprim::exclusive_scan(nullptr, tmp, j->d_vlens, j->d_voffs,
+            if (rocprim::exclusive_scan(nullptr, tmp, j->vf.d_vlens, j->vf.d_voffs,
                                         (uint64_t)0, (size_t)n_alive + 1,
                                         rocprim::plus<uint64_t>(),
                                         j->stream) != hipSuccess) {
                 rcv = RW_E_INTERNAL;
                 break;
             }
-            if (tmp > j->d_scan_tmp_cap) {
-                if (j->d_scan_tmp) hipFree(j->d_scan_tmp);
-                j->d_scan_tmp = nullptr;
-                j->d_scan_tmp_cap = 0;
-                if (hipMalloc(&j->d_scan_tmp, tmp) != hipSuccess) {
+            if (tmp > j->vf.d_scan_tmp_cap) {
+                if (j->vf.d_scan_tmp) hipFree(j->vf.d_scan_tmp);
+                j->vf.d_scan_tmp = nullptr;
+                j->vf.d_scan_tmp_cap = 0;
+                if (hipMalloc(&j->vf.d_scan_tmp, tmp) != hipSuccess) {
                     rcv = RW_E_INTERNAL;
                     break;
                 }
-                j->d_scan_tmp_cap = tmp;
+                j->vf.d_scan_tmp_cap = tmp;
             }
             uint64_t total = 0;
-            if (rocprim::exclusive_scan(j->d_scan_tmp, tmp, j->d_vlens,
-                                        j->d_voffs, (uint64_t)0,
+            if (rocprim::exclusive_scan(j->vf.d_scan_tmp, tmp, j->vf.d_vlens,
+                                        j->vf.d_voffs, (uint64_t)0,
                                         (size_t)n_alive + 1,
                                         rocprim::plus<uint64_t>(),
                                         j->stream) != hipSuccess ||
-                hipMemcpyAsync(&total, j->d_voffs + n_alive, 8,
+                hipMemcpyAsync(&total, j->vf.d_voffs + n_alive, 8,
                                hipMemcpyDeviceToHost, j->stream) != hipSuccess ||
                 hipStreamSynchronize(j->stream) != hipSuccess) {
                 rcv = RW_E_INTERNAL;
@@ -8487,12 +9153,12 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
             uint64_t base = (new_used + VARLEN_COPY_PAD - 1) &
                             ~(uint64_t)(VARLEN_COPY_PAD - 1);
             if (total)
-                varlen_copy_launch(v, sd.arena, j->d_voffs, n_alive, total,
+                varlen_copy_launch(v, sd.arena, j->vf.d_voffs, n_alive, total,
                                    na + base, j->stream);
             uint32_t rblocks = (n_alive + 255) / 256;
             if (rblocks > 4096) rblocks = 4096;
             varlen_rewrite_kernel<<<rblocks, 256, 0, j->stream>>>(
-                sd, c, n_alive, j->d_voffs, base);
+                sd, c, n_alive, j->vf.d_voffs, base);
             if (hipStreamSynchronize(j->stream) != hipSuccess) {
                 rcv = RW_E_INTERNAL;
                 break;
