@@ -490,6 +490,8 @@ int rw_agg_debug_fuse_allowed(void* h);
 /* Launches that carried the flush so far; the policy's dirty-count limit. */
 long long rw_agg_debug_fused_launches(void* h);
 uint32_t rw_agg_debug_fuse_max(void);
+/* Debug: the hash of an n_words key that places it in every state table. */
+uint64_t rw_debug_hash_key(const int64_t* kw, uint32_t nullmask, int n_words);
 
 #ifdef __cplusplus
 }

@@ -67,7 +67,7 @@ static bool gpu_ok() {
 // device helpers
 // ---------------------------------------------------------------------------
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     // splitmix64 finalizer — internal hash placement only (free choice per
     // XxHash64 is cache placement, not output-visible)
     x += 0x9e3779b97f4a7c15ULL;
@@ -76,8 +76,9 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-__device__ __forceinline__ uint64_t hash_key(const int64_t* kw, uint32_t nullmask,
-                                             int KW) {
+__host__ __device__ __forceinline__ uint64_t hash_key(const int64_t* kw,
+                                                      uint32_t nullmask,
+                                                      int KW) {
     uint64_t h = 0x20210401u ^ (uint64_t)nullmask * 0x9e3779b97f4a7c15ULL;
     for (int i = 0; i < KW; i++) h = mix64(h ^ (uint64_t)kw[i]);
     return h;
@@ -4863,6 +4864,12 @@ long long rw_agg_debug_fused_launches(void* h) {
 }
 uint32_t rw_agg_debug_fuse_max(void) { return HashAgg::FUSE_MAX; }
 
+// debug: the key hash every state table places by (table_find_or_insert,
+// jslot_start, jbloom_bit), so tests can aim keys at chosen slots
+uint64_t rw_debug_hash_key(const int64_t* kw, uint32_t nullmask, int n_words) {
+    return hash_key(kw, nullmask, n_words);
+}
+
 int rw_agg_debug_scan(void* h, RwAggDebug* out) {
     auto* agg = (HashAgg*)h;
     size_t cap = (size_t)agg->t.cap_mask + 1;
@@ -5566,6 +5573,10 @@ struct JoinBatchDev {
     // by construction for agg-output inputs like Nexmark q8's): at most one
     // chain push per slot per launch, so the head publish needs no CAS
     uint8_t unique_keys;
+    // no visible row is an Insert: the inner probe's pre-assigned layout
+    // reserves no records for the batch, so a full row store still takes
+    // the deletes that let rw_join_compact make room
+    uint8_t no_insert;
 };
 
 struct JoinOutDev {
@@ -6011,13 +6022,15 @@ __device__ void join_probe_row_noninner(const JoinBatchDev& b, JoinSideDev own,
 // kernel comment below): output region [0, n) is one sparse slot per
 // probe row (ops sentinel 0xFF = empty; the emission cursor starts at n
 // for >1-match overflow), and the batch's record rows are reserved as ONE
-// cursor bump so the kernel needs no cross-lane reservation at all.
+// cursor bump so the kernel needs no cross-lane reservation at all
+// (n_records = n, or 0 for a batch without inserts).
 __global__ void jprobe_setup_kernel(JoinOutDev out, uint32_t* row_cursor,
                                     uint32_t row_cap, uint32_t* row_base,
-                                    uint32_t n) {
+                                    uint32_t n, uint32_t n_records) {
     out.counters[0] = n; // overflow emissions append past the sparse region
-    uint32_t base = atomicAdd(row_cursor, n);
-    if ((uint64_t)base + n > row_cap) atomicExch(&out.counters[1], 3u);
+    uint32_t base = atomicAdd(row_cursor, n_records);
+    if ((uint64_t)base + n_records > row_cap)
+        atomicExch(&out.counters[1], 3u);
     *row_base = base;
 }
 
@@ -6259,7 +6272,8 @@ __global__ __launch_bounds__(256, 6) void join_probe_kernel(
             if (r < r1) {
                 uint32_t myrow = *row_base + r;
                 bool do_insert = active && is_insert;
-                if (myrow < own.row_cap) {
+                // (a batch without inserts reserved no records)
+                if (!b.no_insert && myrow < own.row_cap) {
                     JoinRowHdr* hd2 = jrow(own, myrow);
                     if (do_insert) {
                         long long* hv2 = jvals(hd2);
@@ -7562,6 +7576,11 @@ struct HashJoin {
             if (!(c->vis && !c->vis[r]) && c->ops[r] != RW_OP_INSERT &&
                 c->ops[r] != RW_OP_UPDATE_INSERT)
                 b.all_insert = 0;
+        b.no_insert = !b.all_insert;
+        for (uint32_t r = 0; r < n && b.no_insert; r++)
+            if (!(c->vis && !c->vis[r]) && (c->ops[r] == RW_OP_INSERT ||
+                                            c->ops[r] == RW_OP_UPDATE_INSERT))
+                b.no_insert = 0;
         b.all_valid = 1;
         for (int ci = 0; ci < m.n_cols[s] && b.all_valid; ci++)
             for (uint32_t r = 0; r < n && b.all_valid; r++)
@@ -7610,7 +7629,7 @@ struct HashJoin {
             HIP_TRY(hipMemsetAsync(out.ops, 0xFF, b.n_rows, stream));
             jprobe_setup_kernel<<<1, 1, 0, stream>>>(
                 out, side[s].row_cursor, side[s].row_cap, d_probe_base,
-                b.n_rows);
+                b.n_rows, b.no_insert ? 0u : b.n_rows);
             last_sparse_rows = b.n_rows;
             sparse_out = true;
         }
@@ -8700,6 +8719,7 @@ int rw_join_apply_aggout(void* join_h, void* agg_h, int side,
     b.n_rows = (uint32_t)n_rows;
     b.all_insert = 0; // change stream carries U-/U+ pairs
     b.unique_keys = 0;
+    b.no_insert = 0;
     uint32_t blocks = ((uint32_t)n_rows + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     aggout_to_join_kernel<<<blocks, 256, 0, j->stream>>>(

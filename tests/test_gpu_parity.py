@@ -12,6 +12,7 @@ from rwtest.ffi import (
     AGG_COUNT, AGG_COUNT_STAR, AGG_MAX, AGG_MIN, AGG_SUM, CMP_LT, JOIN_INNER,
     SIDE_LEFT, SIDE_RIGHT, T_I64, T_TS, from_pretty, oracle, rows_multiset,
 )
+from rwtest.streams import join_mix_push, topn_mix_chunk
 
 pytestmark = pytest.mark.gpu
 
@@ -724,19 +725,7 @@ def test_topn_random():
     g, o = _topn_pair(1, 3, [0], [(1, True)], [(2, False)])
     live = []
     for i in range(10):
-        n = 512
-        gk = rng.integers(0, 40, n)
-        ordv = rng.integers(0, 200, n)
-        pk = rng.integers(0, 10**6, n)
-        ops = np.zeros(n, np.uint8)
-        for r in range(n):
-            if live and rng.random() < 0.35:
-                jx = int(rng.integers(0, len(live)))
-                gk[r], ordv[r], pk[r] = live.pop(jx)
-                ops[r] = ffi.OP_DELETE
-            else:
-                live.append((int(gk[r]), int(ordv[r]), int(pk[r])))
-        c = mk_chunk([T_I64, T_I64, T_I64], ops, [gk, ordv, pk])
+        c = topn_mix_chunk(rng, live, 512, 40, 200, 10**6, 0.35)
         g.push(c)
         o.push(c)
         mg = rows_multiset(g.poll_all())
@@ -761,22 +750,8 @@ def test_join_noninner_random(jt):
     o = ffi.HashJoin(oracle(), jt, [T_I64, T_I64], [T_I64, T_I64],
                      key_l=[0], key_r=[0], pk_l=[1], pk_r=[1])
     live = {SIDE_LEFT: [], SIDE_RIGHT: []}
-    pk = 0
     for i in range(10):
-        side = int(rng.integers(0, 2))
-        n = 1024
-        keys = rng.integers(0, 120, n)
-        vals = np.arange(pk, pk + n)
-        pk += n
-        ops = np.zeros(n, np.uint8)
-        for r in range(n):
-            if live[side] and rng.random() < 0.3:
-                jx = int(rng.integers(0, len(live[side])))
-                keys[r], vals[r] = live[side].pop(jx)
-                ops[r] = ffi.OP_DELETE
-            else:
-                live[side].append((int(keys[r]), int(vals[r])))
-        c = mk_chunk([T_I64, T_I64], ops, [keys, vals])
+        side, c = join_mix_push(rng, live, i * 1024, 1024, 120, 0.3)
         g.push(side, c)
         o.push(side, c)
         mg = net_rows(rows_multiset(g.poll_all()))
@@ -997,19 +972,8 @@ def test_topn_with_ties_parity():
                       offset=0, limit=3, with_ties=True)
     live = []
     for i in range(8):
-        n = 512
-        gk = rng.integers(0, 20, n)
-        ordv = rng.integers(0, 6, n)  # heavy ties
-        pk = rng.integers(0, 10**7, n)
-        ops = np.zeros(n, np.uint8)
-        for r in range(n):
-            if live and rng.random() < 0.4:
-                jx = int(rng.integers(0, len(live)))
-                gk[r], ordv[r], pk[r] = live.pop(jx)
-                ops[r] = ffi.OP_DELETE
-            else:
-                live.append((int(gk[r]), int(ordv[r]), int(pk[r])))
-        c = mk_chunk(I3, ops, [gk, ordv, pk])
+        # six order values: heavy ties
+        c = topn_mix_chunk(rng, live, 512, 20, 6, 10**7, 0.4)
         g.push(c)
         o.push(c)
         mg = rows_multiset(g.poll_all())
