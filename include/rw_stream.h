@@ -492,6 +492,10 @@ long long rw_agg_debug_fused_launches(void* h);
 uint32_t rw_agg_debug_fuse_max(void);
 /* Debug: the hash of an n_words key that places it in every state table. */
 uint64_t rw_debug_hash_key(const int64_t* kw, uint32_t nullmask, int n_words);
+/* Debug: device bytes currently held by all of this library's executors,
+ * caller-owned batches and in-flight calls. Process-wide and exact; back at
+ * its earlier value once everything created since has been destroyed. */
+uint64_t rw_debug_dev_bytes_live(void);
 
 #ifdef __cplusplus
 }

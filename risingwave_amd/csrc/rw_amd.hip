@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <optional>
 #include <string>
@@ -37,6 +38,7 @@
 #include "../../include/rw_stream.h"
 #include "../../include/rw_varlen.hpp"
 #include "../../include/rw_xpayload.hpp"
+#include "rw_devmem.hpp"
 
 #define WAVE 64
 
@@ -57,6 +59,35 @@ static thread_local std::string g_err;
             FAIL(RW_E_INTERNAL, "HIP error %s at %s:%d", hipGetErrorString(_e), \
                  __FILE__, __LINE__);                                       \
     } while (0)
+
+// An executor's staging batch (AggBatch / JoinBatchDev), re-made for `cap`
+// rows of `val_bytes`-wide value cells: everything old is freed first, so
+// the peak stays at one batch.
+template <class Batch>
+static int stage_regrow(DevOwner& mem, Batch& b, int n_cols, size_t cap,
+                        size_t val_bytes) {
+    for (int i = 0; i < n_cols; i++) {
+        mem.release(&b.col_vals[i]);
+        mem.release(&b.col_valid[i]);
+    }
+    mem.release(&b.ops);
+    mem.release(&b.vis);
+    for (int i = 0; i < n_cols; i++) {
+        HIP_TRY(mem.alloc(&b.col_vals[i], cap * val_bytes));
+        HIP_TRY(mem.alloc(&b.col_valid[i], cap));
+    }
+    HIP_TRY(mem.alloc(&b.ops, cap));
+    HIP_TRY(mem.alloc(&b.vis, cap));
+    return RW_OK;
+}
+
+// A caller-owned device batch (the bench preload handles): the
+// kernel-argument struct, which is what the handle points at, and beside it
+// the owner of the batch's buffers.
+template <class Batch>
+struct Owned : Batch {
+    DevOwner mem;
+};
 
 static bool gpu_ok() {
     int n = 0;
@@ -2194,7 +2225,10 @@ struct VarlenFetch {
     double vemit_ms = 0, vcopy_ms = 0; // whole materialise / copy kernel
     uint64_t vemit_bytes = 0, vemit_launches = 0;
 
+    DevOwner mem;
+
     int ensure_vscratch(uint32_t n);
+    int ensure_scan_tmp(size_t tmp); // rocPRIM scan temporary storage
     int fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
               std::vector<uint64_t>& offs, std::vector<uint8_t>& bytes,
               bool timed, hipStream_t stream);
@@ -2364,37 +2398,18 @@ struct HashAgg {
     std::vector<RwAggCall> calls;
     int KW, n_calls, out_width;
     std::vector<uint8_t> out_types;
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
+    // every device buffer of this executor (rw_devmem.hpp); the destructor
+    // frees them after the stream has drained and before it is destroyed
+    DevOwner mem;
     AggTableDev t{};
     uint32_t capacity;
     // staging (host-pinned mirrors reused per push)
     AggBatch stage{};
     uint32_t stage_cap = 0;
-    // kernel timing (HIP events on this executor's own stream). Event pairs
-    // live in a ring and are read back lazily — a per-step
-    // hipEventSynchronize costs a full host round-trip (~45 us, 3x the
-    // kernel itself at q7 sizes), so the timed region must stay async.
-    static constexpr int EV_RING = 256;
-    hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {};
-    uint8_t ev_pending[EV_RING] = {};
-    uint64_t ev_head = 0;
-    double apply_ms_total = 0;
+    // kernel timing (HIP events on this executor's own stream)
+    EventRing ring; // ring.ms_total: apply kernel time
     uint64_t apply_launches = 0, apply_rows = 0;
-
-    int ev_harvest(int slot) {
-        if (!ev_pending[slot]) return RW_OK;
-        HIP_TRY(hipEventSynchronize(ev1[slot]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0[slot], ev1[slot]));
-        apply_ms_total += ms;
-        ev_pending[slot] = 0;
-        return RW_OK;
-    }
-    int ev_harvest_all() {
-        for (int s = 0; s < EV_RING; s++)
-            if (ev_harvest(s) != RW_OK) return RW_E_INTERNAL;
-        return RW_OK;
-    }
     // pending outputs
     std::vector<RwChunk*> outq;
     // checkpoint spill buffer (§8f-2): state-table KV deltas, accumulated at
@@ -2465,16 +2480,16 @@ struct HashAgg {
                                                 : IN_STRINGS_DEFAULT);
         uint32_t tcap = 2;
         while (tcap < want && tcap < (1u << 31)) tcap <<= 1;
-        HIP_TRY(hipMalloc(&in.arena, acap));
+        HIP_TRY(mem.alloc(&in.arena, acap));
         HIP_TRY(hipMemset(in.arena, 0, rwvarlen::AGG_ARENA_HEADER));
         in.arena_cap = acap;
-        HIP_TRY(hipMalloc(&in.slots, (size_t)tcap * 8));
+        HIP_TRY(mem.alloc(&in.slots, (size_t)tcap * 8));
         HIP_TRY(hipMemset(in.slots, 0, (size_t)tcap * 8));
         in.cap_mask = tcap - 1;
-        HIP_TRY(hipMalloc(&in.tail, 8));
+        HIP_TRY(mem.alloc(&in.tail, 8));
         unsigned long long t0 = rwvarlen::AGG_ARENA_HEADER;
         HIP_TRY(hipMemcpy(in.tail, &t0, 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&in.ctr, 8));
+        HIP_TRY(mem.alloc(&in.ctr, 8));
         HIP_TRY(hipMemset(in.ctr, 0, 8));
         in.err = &t.counters[2];
         in_ready = true;
@@ -2510,12 +2525,7 @@ struct HashAgg {
         if (need > in.arena_cap) {
             uint64_t cap = in.arena_cap;
             while (cap < need) cap *= 2;
-            uint8_t* na = nullptr;
-            HIP_TRY(hipMalloc(&na, cap));
-            HIP_TRY(hipMemcpy(na, in.arena, in_tail_known,
-                              hipMemcpyDeviceToDevice));
-            hipFree(in.arena);
-            in.arena = na;
+            HIP_TRY(mem.regrow(&in.arena, cap, in_tail_known));
             in.arena_cap = cap;
         }
         return RW_OK;
@@ -2534,14 +2544,14 @@ struct HashAgg {
             FAIL(RW_E_INVAL, "varchar group-key intern table > 2^31 slots");
         if (ncap != tcap) {
             uint64_t* ns = nullptr;
-            HIP_TRY(hipMalloc(&ns, ncap * 8));
+            HIP_TRY(mem.alloc(&ns, ncap * 8));
             HIP_TRY(hipMemsetAsync(ns, 0, ncap * 8, stream));
             agg_intern_rehash_kernel<<<grid_for((uint32_t)tcap), 256, 0,
                                        stream>>>(in.slots, (uint32_t)tcap, ns,
                                                  (uint32_t)(ncap - 1),
                                                  in.arena);
             HIP_TRY(hipStreamSynchronize(stream));
-            hipFree(in.slots);
+            mem.release(&in.slots);
             in.slots = ns;
             in.cap_mask = (uint32_t)(ncap - 1);
         }
@@ -2558,25 +2568,22 @@ struct HashAgg {
             FAIL(RW_E_INVAL, "varchar group-key batch too large");
         if (in_stg_cap < bytes + 1) {
             HIP_TRY(hipStreamSynchronize(stream));
-            if (in_stg) hipFree(in_stg);
-            in_stg = nullptr;
             in_stg_cap = 0;
             uint64_t cap = 1ull << 16;
             while (cap < bytes + 1) cap <<= 1;
-            HIP_TRY(hipMalloc(&in_stg, cap));
+            HIP_TRY(mem.regrow(&in_stg, cap));
             in_stg_cap = cap;
         }
         in.stg = in_stg;
         if (in_row_cap < cells) {
             HIP_TRY(hipStreamSynchronize(stream));
-            if (in.rowslot) hipFree(in.rowslot);
-            if (in.winners) hipFree(in.winners);
-            in.rowslot = in.winners = nullptr;
+            mem.release(&in.rowslot);
+            mem.release(&in.winners);
             in_row_cap = 0;
             uint64_t cap = 4096;
             while (cap < cells) cap <<= 1;
-            HIP_TRY(hipMalloc(&in.rowslot, cap * 4));
-            HIP_TRY(hipMalloc(&in.winners, cap * 4));
+            HIP_TRY(mem.alloc(&in.rowslot, cap * 4));
+            HIP_TRY(mem.alloc(&in.winners, cap * 4));
             in_row_cap = (uint32_t)(cap > UINT32_MAX ? UINT32_MAX : cap);
         }
         rc = intern_arena_ensure(bytes);
@@ -2728,7 +2735,7 @@ struct HashAgg {
     // apply_range's HIP event pair costs ~5 us of a ~62 us epoch step on
     // this runtime: it is recorded on one launch in
     // 16, the first after a stats reset included, and only recorded
-    // launches count in apply_launches / apply_rows / apply_ms_total, so the
+    // launches count in apply_launches / apply_rows / ring.ms_total, so the
     // averages stay averages (A/B via RW_AGG_EVENT_EVERY=1).
     static uint32_t ev_every() {
         static uint32_t n = [] {
@@ -2869,37 +2876,37 @@ struct HashAgg {
         HIP_TRY(hipStreamCreate(&stream));
         size_t cap = capacity;
         t.cap_mask = capacity - 1;
-        HIP_TRY(hipMalloc(&t.state, cap * 4));
+        HIP_TRY(mem.alloc(&t.state, cap * 4));
         HIP_TRY(hipMemset(t.state, 0, cap * 4));
-        HIP_TRY(hipMalloc(&t.keys, cap * KW * 8));
-        HIP_TRY(hipMalloc(&t.key_nulls, cap * 4));
-        HIP_TRY(hipMalloc(&t.acc, cap * n_calls * 8));
-        HIP_TRY(hipMalloc(&t.has, cap * n_calls));
+        HIP_TRY(mem.alloc(&t.keys, cap * KW * 8));
+        HIP_TRY(mem.alloc(&t.key_nulls, cap * 4));
+        HIP_TRY(mem.alloc(&t.acc, cap * n_calls * 8));
+        HIP_TRY(mem.alloc(&t.has, cap * n_calls));
         HIP_TRY(hipMemset(t.has, 0, cap * n_calls));
-        HIP_TRY(hipMalloc(&t.prev, cap * n_calls * 8));
-        HIP_TRY(hipMalloc(&t.prev_null, cap * n_calls));
-        HIP_TRY(hipMalloc(&t.has_prev, cap));
+        HIP_TRY(mem.alloc(&t.prev, cap * n_calls * 8));
+        HIP_TRY(mem.alloc(&t.prev_null, cap * n_calls));
+        HIP_TRY(mem.alloc(&t.has_prev, cap));
         HIP_TRY(hipMemset(t.has_prev, 0, cap));
-        HIP_TRY(hipMalloc(&t.dirty_flag, cap * 4));
+        HIP_TRY(mem.alloc(&t.dirty_flag, cap * 4));
         HIP_TRY(hipMemset(t.dirty_flag, 0, cap * 4));
-        HIP_TRY(hipMalloc(&t.dirty_list, cap * 4));
-        HIP_TRY(hipMalloc(&t.counters, AGG_CTR_WORDS * 4));
+        HIP_TRY(mem.alloc(&t.dirty_list, cap * 4));
+        HIP_TRY(mem.alloc(&t.counters, AGG_CTR_WORDS * 4));
         HIP_TRY(hipMemset(t.counters, 0, AGG_CTR_WORDS * 4));
         t.out_capacity = 1u << 22;
-        HIP_TRY(hipMalloc(&t.out_vals, (size_t)t.out_capacity * out_width * 8));
-        HIP_TRY(hipMalloc(&t.out_nulls, (size_t)t.out_capacity * out_width));
-        HIP_TRY(hipMalloc(&t.out_ops, t.out_capacity));
+        HIP_TRY(mem.alloc(&t.out_vals, (size_t)t.out_capacity * out_width * 8));
+        HIP_TRY(mem.alloc(&t.out_nulls, (size_t)t.out_capacity * out_width));
+        HIP_TRY(mem.alloc(&t.out_ops, t.out_capacity));
         t.n_dec = n_dec;
         if (n_dec) {
-            HIP_TRY(hipMalloc(&t.dsum, (size_t)n_dec * 4 * cap * 8));
+            HIP_TRY(mem.alloc(&t.dsum, (size_t)n_dec * 4 * cap * 8));
             HIP_TRY(hipMemset(t.dsum, 0, (size_t)n_dec * 4 * cap * 8));
-            HIP_TRY(hipMalloc(&t.dscl, (size_t)n_dec * cap * 4));
+            HIP_TRY(mem.alloc(&t.dscl, (size_t)n_dec * cap * 4));
             HIP_TRY(hipMemset(t.dscl, 0, (size_t)n_dec * cap * 4));
-            HIP_TRY(hipMalloc(&t.dspec, (size_t)n_dec * 3 * cap * 8));
+            HIP_TRY(mem.alloc(&t.dspec, (size_t)n_dec * 3 * cap * 8));
             HIP_TRY(hipMemset(t.dspec, 0, (size_t)n_dec * 3 * cap * 8));
-            HIP_TRY(hipMalloc(&t.out_vals2,
+            HIP_TRY(mem.alloc(&t.out_vals2,
                               (size_t)t.out_capacity * out_width * 8));
-            HIP_TRY(hipMalloc(&t.prev2, (size_t)n_calls * cap * 8));
+            HIP_TRY(mem.alloc(&t.prev2, (size_t)n_calls * cap * 8));
             HIP_TRY(hipMemset(t.prev2, 0, (size_t)n_calls * cap * 8));
         }
         t.n_sk = (int)stream_key.size();
@@ -2910,22 +2917,22 @@ struct HashAgg {
                 t.mrow_cap = 1;
                 while (t.mrow_cap < want && t.mrow_cap < (1u << 28)) t.mrow_cap <<= 1;
             }
-            HIP_TRY(hipMalloc(&t.mheads, (size_t)n_minput * cap * 4));
+            HIP_TRY(mem.alloc(&t.mheads, (size_t)n_minput * cap * 4));
             HIP_TRY(hipMemset(t.mheads, 0xFF, (size_t)n_minput * cap * 4));
-            HIP_TRY(hipMalloc(&t.mval, (size_t)t.mrow_cap * 8));
-            HIP_TRY(hipMalloc(&t.mval_null, t.mrow_cap));
+            HIP_TRY(mem.alloc(&t.mval, (size_t)t.mrow_cap * 8));
+            HIP_TRY(mem.alloc(&t.mval_null, t.mrow_cap));
             size_t nsk = t.n_sk ? t.n_sk : 1;
-            HIP_TRY(hipMalloc(&t.msk, nsk * t.mrow_cap * 8));
-            HIP_TRY(hipMalloc(&t.msk_null, nsk * t.mrow_cap));
-            HIP_TRY(hipMalloc(&t.mnext, (size_t)t.mrow_cap * 4));
-            HIP_TRY(hipMalloc(&t.malive, (size_t)t.mrow_cap * 4));
-            HIP_TRY(hipMalloc(&t.mcursor, 4));
+            HIP_TRY(mem.alloc(&t.msk, nsk * t.mrow_cap * 8));
+            HIP_TRY(mem.alloc(&t.msk_null, nsk * t.mrow_cap));
+            HIP_TRY(mem.alloc(&t.mnext, (size_t)t.mrow_cap * 4));
+            HIP_TRY(mem.alloc(&t.malive, (size_t)t.mrow_cap * 4));
+            HIP_TRY(mem.alloc(&t.mcursor, 4));
             HIP_TRY(hipMemset(t.mcursor, 0, 4));
-            HIP_TRY(hipMalloc(&t.mslot, (size_t)t.mrow_cap * 4));
-            HIP_TRY(hipMalloc(&t.mcall, t.mrow_cap));
+            HIP_TRY(mem.alloc(&t.mslot, (size_t)t.mrow_cap * 4));
+            HIP_TRY(mem.alloc(&t.mcall, t.mrow_cap));
             t.mkilled_cap = 1u << 22;
-            HIP_TRY(hipMalloc(&t.mkilled, (size_t)t.mkilled_cap * 4));
-            HIP_TRY(hipMalloc(&t.mkilled_cursor, 4));
+            HIP_TRY(mem.alloc(&t.mkilled, (size_t)t.mkilled_cap * 4));
+            HIP_TRY(mem.alloc(&t.mkilled_cursor, 4));
             HIP_TRY(hipMemset(t.mkilled_cursor, 0, 4));
         }
         agg_init_kernel<<<2048, 256, 0, stream>>>(t, n_calls, cd(0), cd(1), cd(2),
@@ -2938,30 +2945,14 @@ struct HashAgg {
 
     int ensure_stage(uint32_t n_rows) {
         if (stage_cap >= n_rows) return RW_OK;
-        free_stage();
+        stage_cap = 0;
         uint32_t cap = 4096;
         while (cap < n_rows) cap <<= 1;
-        for (int i = 0; i < n_batch_slots(); i++) {
-            // 16 B/row so decimal slots (2 words/row) fit
-            HIP_TRY(hipMalloc(&stage.col_vals[i], (size_t)cap * 16));
-            HIP_TRY(hipMalloc(&stage.col_valid[i], cap));
-        }
-        HIP_TRY(hipMalloc(&stage.ops, cap));
-        HIP_TRY(hipMalloc(&stage.vis, cap));
+        // 16 B/row so decimal slots (2 words/row) fit
+        int rc = stage_regrow(mem, stage, n_batch_slots(), cap, 16);
+        if (rc != RW_OK) return rc;
         stage_cap = cap;
         return RW_OK;
-    }
-    void free_stage() {
-        for (int i = 0; i < n_batch_slots(); i++) {
-            if (stage.col_vals[i]) hipFree(stage.col_vals[i]);
-            if (stage.col_valid[i]) hipFree(stage.col_valid[i]);
-            stage.col_vals[i] = nullptr;
-            stage.col_valid[i] = nullptr;
-        }
-        if (stage.ops) hipFree(stage.ops);
-        if (stage.vis) hipFree(stage.vis);
-        stage.ops = stage.vis = nullptr;
-        stage_cap = 0;
     }
 
     // upload one host chunk into a device AggBatch (batch cols = group key
@@ -3170,15 +3161,8 @@ struct HashAgg {
               const std::vector<uint32_t>& seg_bounds = {}) {
         int slot = -1;
         if (timed) {
-            slot = (int)(ev_head++ % EV_RING);
-            if (!ev0[slot]) {
-                HIP_TRY(hipEventCreate(&ev0[slot]));
-                HIP_TRY(hipEventCreate(&ev1[slot]));
-            }
-            // reclaim the slot's previous measurement (long complete by the
-            // time the ring wraps) without stalling the current step
-            if (ev_harvest(slot) != RW_OK) return RW_E_INTERNAL;
-            HIP_TRY(hipEventRecord(ev0[slot], stream));
+            slot = ring.begin(stream);
+            if (slot < 0) FAIL(RW_E_INTERNAL, "HIP event error (apply timing)");
         }
         uint32_t start = 0;
         for (uint32_t bnd : seg_bounds) {
@@ -3187,8 +3171,7 @@ struct HashAgg {
         }
         if (start < b.n_rows) launch_apply(b, start, b.n_rows);
         if (timed) {
-            HIP_TRY(hipEventRecord(ev1[slot], stream));
-            ev_pending[slot] = 1;
+            HIP_TRY(ring.end(slot, stream));
             apply_launches++;
             apply_rows += b.n_rows;
         }
@@ -3203,20 +3186,14 @@ struct HashAgg {
         int slot = -1;
         timed = timed && ev_seq++ % ev_every() == 0;
         if (timed) {
-            slot = (int)(ev_head++ % EV_RING);
-            if (!ev0[slot]) {
-                HIP_TRY(hipEventCreate(&ev0[slot]));
-                HIP_TRY(hipEventCreate(&ev1[slot]));
-            }
-            if (ev_harvest(slot) != RW_OK) return RW_E_INTERNAL;
-            HIP_TRY(hipEventRecord(ev0[slot], stream));
+            slot = ring.begin(stream);
+            if (slot < 0) FAIL(RW_E_INTERNAL, "HIP event error (apply timing)");
         }
         bool did = launch_apply(b, r0, r1, fuse);
         if (fused) *fused = did;
         fused_launches += did;
         if (timed) {
-            HIP_TRY(hipEventRecord(ev1[slot], stream));
-            ev_pending[slot] = 1;
+            HIP_TRY(ring.end(slot, stream));
             apply_launches++;
             apply_rows += r1 - r0;
         }
@@ -3276,14 +3253,14 @@ struct HashAgg {
             dedup_cap_mask = (uint32_t)(cap - 1);
             for (size_t di = 0; di < distinct_slots.size(); di++) {
                 JoinSlot* sl = nullptr;
-                HIP_TRY(hipMalloc(&sl, cap * sizeof(JoinSlot)));
+                HIP_TRY(mem.alloc(&sl, cap * sizeof(JoinSlot)));
                 dedup_init_kernel<<<2048, 256, 0, stream>>>(sl, cap);
                 dedup_slots.push_back(sl);
                 uint32_t *df = nullptr, *dl = nullptr, *dn = nullptr;
-                HIP_TRY(hipMalloc(&df, cap * 4));
+                HIP_TRY(mem.alloc(&df, cap * 4));
                 HIP_TRY(hipMemset(df, 0, cap * 4));
-                HIP_TRY(hipMalloc(&dl, cap * 4));
-                HIP_TRY(hipMalloc(&dn, 4));
+                HIP_TRY(mem.alloc(&dl, cap * 4));
+                HIP_TRY(mem.alloc(&dn, 4));
                 HIP_TRY(hipMemset(dn, 0, 4));
                 ddirty_flag.push_back(df);
                 ddirty_list.push_back(dl);
@@ -3292,11 +3269,11 @@ struct HashAgg {
             }
         }
         if (hidden_cap < n) {
-            for (auto*& hb : hidden_bufs)
-                if (hb) hipFree(hb);
+            hidden_cap = 0;
+            for (auto*& hb : hidden_bufs) mem.release(&hb);
             hidden_bufs.assign(distinct_slots.size(), nullptr);
             for (size_t di = 0; di < distinct_slots.size(); di++)
-                HIP_TRY(hipMalloc(&hidden_bufs[di], n));
+                HIP_TRY(mem.alloc(&hidden_bufs[di], n));
             hidden_cap = n;
         }
         return RW_OK;
@@ -3320,31 +3297,16 @@ struct HashAgg {
         if (ecap >= need) return RW_OK;
         uint64_t cap = ecap ? ecap : (1ull << 21);
         while (cap < need) cap <<= 1;
-        AggBatch nb{};
+        // the last epoch's apply launch may still read the old buffers
+        HIP_TRY(hipStreamSynchronize(stream));
+        ecap = 0;
         int slots = n_batch_slots();
         for (int i = 0; i < slots; i++) {
-            HIP_TRY(hipMalloc(&nb.col_vals[i], cap * 8));
-            HIP_TRY(hipMalloc(&nb.col_valid[i], cap));
-            if (ecap) {
-                HIP_TRY(hipMemcpyAsync(nb.col_vals[i], ebuf.col_vals[i],
-                                       erows * 8, hipMemcpyDeviceToDevice,
-                                       stream));
-                HIP_TRY(hipMemcpyAsync(nb.col_valid[i], ebuf.col_valid[i],
-                                       erows, hipMemcpyDeviceToDevice,
-                                       stream));
-            }
+            HIP_TRY(mem.regrow(&ebuf.col_vals[i], cap * 8, erows * 8, stream,
+                               true));
+            HIP_TRY(mem.regrow(&ebuf.col_valid[i], cap, erows, stream, true));
         }
-        HIP_TRY(hipMalloc(&nb.ops, cap));
-        if (ecap)
-            HIP_TRY(hipMemcpyAsync(nb.ops, ebuf.ops, erows,
-                                   hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        for (int i = 0; i < slots && ecap; i++) {
-            hipFree(ebuf.col_vals[i]);
-            hipFree(ebuf.col_valid[i]);
-        }
-        if (ecap) hipFree(ebuf.ops);
-        ebuf = nb;
+        HIP_TRY(mem.regrow(&ebuf.ops, cap, erows, stream, true));
         ecap = cap;
         return RW_OK;
     }
@@ -3454,18 +3416,14 @@ struct HashAgg {
         uint64_t cap = t.out_capacity;
         while (cap < need) cap <<= 1;
         if (cap > UINT32_MAX) FAIL(RW_E_INVAL, "flush output > 4G rows");
-        hipFree(t.out_vals);
-        hipFree(t.out_nulls);
-        hipFree(t.out_ops);
-        t.out_vals = nullptr; t.out_nulls = nullptr; t.out_ops = nullptr;
-        HIP_TRY(hipMalloc(&t.out_vals, (size_t)cap * out_width * 8));
-        HIP_TRY(hipMalloc(&t.out_nulls, (size_t)cap * out_width));
-        HIP_TRY(hipMalloc(&t.out_ops, cap));
-        if (n_dec) {
-            hipFree(t.out_vals2);
-            t.out_vals2 = nullptr;
-            HIP_TRY(hipMalloc(&t.out_vals2, (size_t)cap * out_width * 8));
-        }
+        mem.release(&t.out_vals);
+        mem.release(&t.out_nulls);
+        mem.release(&t.out_ops);
+        HIP_TRY(mem.alloc(&t.out_vals, (size_t)cap * out_width * 8));
+        HIP_TRY(mem.alloc(&t.out_nulls, (size_t)cap * out_width));
+        HIP_TRY(mem.alloc(&t.out_ops, cap));
+        if (n_dec)
+            HIP_TRY(mem.regrow(&t.out_vals2, (size_t)cap * out_width * 8));
         t.out_capacity = (uint32_t)cap;
         return RW_OK;
     }
@@ -3762,8 +3720,9 @@ struct HashAgg {
         std::vector<uint32_t> slots_h(n);
         HIP_TRY(hipMemcpy(slots_h.data(), ddirty_list[di], (size_t)n * 4,
                           hipMemcpyDeviceToHost));
+        DevOwner tmp;
         DedupDirtyRec* d_out = nullptr;
-        HIP_TRY(hipMalloc(&d_out, (size_t)n * sizeof(DedupDirtyRec)));
+        HIP_TRY(tmp.alloc(&d_out, (size_t)n * sizeof(DedupDirtyRec)));
         dedup_gather_kernel<<<grid_for(n), 256, 0, stream>>>(
             dedup_slots[di], ddirty_flag[di], ddirty_list[di], ddirty_n[di],
             d_out);
@@ -3771,7 +3730,7 @@ struct HashAgg {
         int rc_cp = hipMemcpy(recs.data(), d_out,
                               (size_t)n * sizeof(DedupDirtyRec),
                               hipMemcpyDeviceToHost);
-        hipFree(d_out);
+        tmp.release(&d_out);
         if (rc_cp != hipSuccess) FAIL(RW_E_INTERNAL, "dedup gather copy");
         HIP_TRY(hipMemset(ddirty_n[di], 0, 4));
         std::vector<uint8_t> key_types(out_types.begin(),
@@ -3885,11 +3844,12 @@ struct HashAgg {
         long long* dkeys = nullptr;
         uint32_t *dnulls = nullptr, *dcounts = nullptr, *dslots_out = nullptr,
                  *derr = nullptr;
-        HIP_TRY(hipMalloc(&dkeys, keys.size() * 8));
-        HIP_TRY(hipMalloc(&dnulls, (size_t)n * 4));
-        HIP_TRY(hipMalloc(&dcounts, (size_t)n * 4));
-        HIP_TRY(hipMalloc(&dslots_out, (size_t)n * 4));
-        HIP_TRY(hipMalloc(&derr, 4));
+        DevOwner tmp;
+        HIP_TRY(tmp.alloc(&dkeys, keys.size() * 8));
+        HIP_TRY(tmp.alloc(&dnulls, (size_t)n * 4));
+        HIP_TRY(tmp.alloc(&dcounts, (size_t)n * 4));
+        HIP_TRY(tmp.alloc(&dslots_out, (size_t)n * 4));
+        HIP_TRY(tmp.alloc(&derr, 4));
         HIP_TRY(hipMemcpy(dkeys, keys.data(), keys.size() * 8,
                           hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dnulls, nulls.data(), (size_t)n * 4,
@@ -3909,11 +3869,7 @@ struct HashAgg {
                       hipMemcpyDeviceToHost);
             hipMemcpy(&errv, derr, 4, hipMemcpyDeviceToHost);
         }
-        hipFree(dkeys);
-        hipFree(dnulls);
-        hipFree(dcounts);
-        hipFree(dslots_out);
-        hipFree(derr);
+        tmp.release_all();
         if (rc_s != RW_OK) FAIL(RW_E_INTERNAL, "dedup restore sync failed");
         if (errv) FAIL(RW_E_INTERNAL, "dedup restore overflow (code %u)", errv);
         auto& persisted = dedup_persisted[di];
@@ -4241,12 +4197,13 @@ struct HashAgg {
         uint8_t* dmn = nullptr;
         long long* dsk = nullptr;
         uint8_t* dskn = nullptr;
-        HIP_TRY(hipMalloc(&dgk, gk.size() * 8));
-        HIP_TRY(hipMalloc(&dgn, gn.size() * 4));
-        HIP_TRY(hipMalloc(&dmv, mv.size() * 8));
-        HIP_TRY(hipMalloc(&dmn, mn.size()));
-        HIP_TRY(hipMalloc(&dsk, sks.size() * 8 + 8));
-        HIP_TRY(hipMalloc(&dskn, skns.size() + 1));
+        DevOwner tmp;
+        HIP_TRY(tmp.alloc(&dgk, gk.size() * 8));
+        HIP_TRY(tmp.alloc(&dgn, gn.size() * 4));
+        HIP_TRY(tmp.alloc(&dmv, mv.size() * 8));
+        HIP_TRY(tmp.alloc(&dmn, mn.size()));
+        HIP_TRY(tmp.alloc(&dsk, sks.size() * 8 + 8));
+        HIP_TRY(tmp.alloc(&dskn, skns.size() + 1));
         HIP_TRY(hipMemcpy(dgk, gk.data(), gk.size() * 8,
                           hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dgn, gn.data(), gn.size() * 4,
@@ -4264,12 +4221,7 @@ struct HashAgg {
             t, KW, mi, dgk, dgn, dmv, dmn, dsk, dskn, n);
         int rc2 = hipStreamSynchronize(stream) == hipSuccess ? RW_OK
                                                              : RW_E_INTERNAL;
-        hipFree(dgk);
-        hipFree(dgn);
-        hipFree(dmv);
-        hipFree(dmn);
-        hipFree(dsk);
-        hipFree(dskn);
+        tmp.release_all();
         if (rc2 != RW_OK) FAIL(RW_E_INTERNAL, "minput restore sync failed");
         int rc3 = check_overflow();
         if (rc3 != RW_OK) return rc3;
@@ -4374,68 +4326,10 @@ struct HashAgg {
     }
 
     ~HashAgg() {
-        free_stage();
-        if (in_ready) {
-            hipFree(in.arena);
-            hipFree(in.slots);
-            hipFree(in.tail);
-            hipFree(in.ctr);
-        }
-        if (in_stg) hipFree(in_stg);
-        if (in.rowslot) hipFree(in.rowslot);
-        if (in.winners) hipFree(in.winners);
         for (auto ev : in_ev)
             if (ev) hipEventDestroy(ev);
-        if (ecap) {
-            for (int i = 0; i < n_batch_slots(); i++) {
-                hipFree(ebuf.col_vals[i]);
-                hipFree(ebuf.col_valid[i]);
-            }
-            hipFree(ebuf.ops);
-        }
-        for (int s = 0; s < EV_RING; s++)
-            if (ev0[s]) {
-                hipEventDestroy(ev0[s]);
-                hipEventDestroy(ev1[s]);
-            }
-        if (t.state) {
-            hipFree(t.state);
-            hipFree(t.keys);
-            hipFree(t.key_nulls);
-            hipFree(t.acc);
-            hipFree(t.has);
-            hipFree(t.prev);
-            hipFree(t.prev_null);
-            hipFree(t.has_prev);
-            hipFree(t.dirty_flag);
-            hipFree(t.dirty_list);
-            hipFree(t.counters);
-            hipFree(t.out_vals);
-            hipFree(t.out_nulls);
-            hipFree(t.out_ops);
-            if (t.dsum) {
-                hipFree(t.dsum);
-                hipFree(t.dscl);
-                hipFree(t.dspec);
-                hipFree(t.out_vals2);
-                hipFree(t.prev2);
-            }
-            if (t.mheads) {
-                hipFree(t.mheads);
-                hipFree(t.mval);
-                hipFree(t.mval_null);
-                hipFree(t.msk);
-                hipFree(t.msk_null);
-                hipFree(t.mnext);
-                hipFree(t.malive);
-                hipFree(t.mcursor);
-                hipFree(t.mslot);
-                hipFree(t.mcall);
-                hipFree(t.mkilled);
-                hipFree(t.mkilled_cursor);
-            }
-            hipStreamDestroy(stream);
-        }
+        mem.release_all(); // device memory goes before the stream
+        if (stream) hipStreamDestroy(stream);
         for (auto* c : outq) rw_chunk_free(c);
     }
 };
@@ -4607,14 +4501,14 @@ void* rw_agg_bench_preload(void* h, const RwChunk* c) {
                 "varchar group keys";
         return nullptr;
     }
-    auto* b = new AggBatch{};
+    auto b = std::make_unique<Owned<AggBatch>>();
     uint32_t n = c->n_rows;
     for (int i = 0; i < agg->n_batch_slots(); i++) {
         // 16 B/row so decimal slots (2 words/row) fit
-        if (hipMalloc(&b->col_vals[i], (size_t)n * 16) != hipSuccess) return nullptr;
-        if (hipMalloc(&b->col_valid[i], n) != hipSuccess) return nullptr;
+        if (b->mem.alloc(&b->col_vals[i], (size_t)n * 16) != hipSuccess) return nullptr;
+        if (b->mem.alloc(&b->col_valid[i], n) != hipSuccess) return nullptr;
     }
-    if (hipMalloc(&b->ops, n) != hipSuccess) return nullptr;
+    if (b->mem.alloc(&b->ops, n) != hipSuccess) return nullptr;
     b->vis = nullptr;
     b->n_rows = n;
     AggBatch stage_save = agg->stage;
@@ -4625,13 +4519,10 @@ void* rw_agg_bench_preload(void* h, const RwChunk* c) {
     int rc = agg->upload(c, &out, true);
     agg->stage = stage_save;
     agg->stage_cap = cap_save;
-    if (rc != RW_OK) {
-        delete b;
-        return nullptr;
-    }
-    *b = out; // keep the computed fields (n_rows, dense, vis)
+    if (rc != RW_OK) return nullptr;
+    (AggBatch&)*b = out; // keep the computed fields (n_rows, dense, vis)
     hipStreamSynchronize(agg->stream);
-    return b;
+    return static_cast<AggBatch*>(b.release());
 }
 
 int rw_agg_bench_apply(void* h, void* batch) {
@@ -4821,10 +4712,10 @@ int rw_agg_apply_flush_launch(void* h, void* batch, uint32_t r0, uint32_t r1,
 
 int rw_agg_kernel_stats(void* h, RwKernelStats* out) {
     auto* agg = (HashAgg*)h;
-    if (agg->ev_harvest_all() != RW_OK)
+    if (!agg->ring.harvest_all())
         FAIL(RW_E_INTERNAL, "event harvest failed");
     out->launches = agg->apply_launches;
-    out->total_ms = agg->apply_ms_total;
+    out->total_ms = agg->ring.ms_total;
     out->rows = agg->apply_rows;
     return RW_OK;
 }
@@ -4866,6 +4757,8 @@ uint32_t rw_agg_debug_fuse_max(void) { return HashAgg::FUSE_MAX; }
 
 // debug: the key hash every state table places by (table_find_or_insert,
 // jslot_start, jbloom_bit), so tests can aim keys at chosen slots
+uint64_t rw_debug_dev_bytes_live(void) { return g_dev_bytes_live.load(); }
+
 uint64_t rw_debug_hash_key(const int64_t* kw, uint32_t nullmask, int n_words) {
     return hash_key(kw, nullmask, n_words);
 }
@@ -4989,10 +4882,11 @@ int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
     long long* dvals = nullptr;
     uint8_t* dvnulls = nullptr;
     long long* dvals2 = nullptr;
-    HIP_TRY(hipMalloc(&dkeys, keys.size() * 8));
-    HIP_TRY(hipMalloc(&dknulls, knulls.size() * 4));
-    HIP_TRY(hipMalloc(&dvals, vals.size() * 8));
-    HIP_TRY(hipMalloc(&dvnulls, vnulls.size()));
+    DevOwner tmp;
+    HIP_TRY(tmp.alloc(&dkeys, keys.size() * 8));
+    HIP_TRY(tmp.alloc(&dknulls, knulls.size() * 4));
+    HIP_TRY(tmp.alloc(&dvals, vals.size() * 8));
+    HIP_TRY(tmp.alloc(&dvnulls, vnulls.size()));
     HIP_TRY(hipMemcpy(dkeys, keys.data(), keys.size() * 8,
                       hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dknulls, knulls.data(), knulls.size() * 4,
@@ -5002,7 +4896,7 @@ int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
     HIP_TRY(hipMemcpy(dvnulls, vnulls.data(), vnulls.size(),
                       hipMemcpyHostToDevice));
     if (agg->n_dec) {
-        HIP_TRY(hipMalloc(&dvals2, vals2.size() * 8));
+        HIP_TRY(tmp.alloc(&dvals2, vals2.size() * 8));
         HIP_TRY(hipMemcpy(dvals2, vals2.data(), vals2.size() * 8,
                           hipMemcpyHostToDevice));
     }
@@ -5024,25 +4918,14 @@ int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
             ic.stride = (uint32_t)KW;
             rcv = agg->intern_run(ic);
         }
-        if (rcv != RW_OK) {
-            hipFree(dkeys);
-            hipFree(dknulls);
-            hipFree(dvals);
-            hipFree(dvnulls);
-            if (dvals2) hipFree(dvals2);
-            return rcv;
-        }
+        if (rcv != RW_OK) return rcv;
     }
     agg_restore_kernel<<<agg->grid_for(n), 256, 0, agg->stream>>>(
         agg->t, KW, nc, dkeys, dknulls, dvals, dvnulls, dvals2, n,
         agg->eowc ? 0 : 1, agg->cd(0), agg->cd(1), agg->cd(2), agg->cd(3));
     int rc = hipStreamSynchronize(agg->stream) == hipSuccess ? RW_OK
                                                              : RW_E_INTERNAL;
-    hipFree(dkeys);
-    hipFree(dknulls);
-    hipFree(dvals);
-    hipFree(dvnulls);
-    if (dvals2) hipFree(dvals2);
+    tmp.release_all();
     if (rc != RW_OK) FAIL(RW_E_INTERNAL, "restore sync failed");
     return agg->check_overflow();
 }
@@ -5083,9 +4966,9 @@ void rw_spill_free(uint8_t* buf) { free(buf); }
 
 int rw_agg_stats_reset(void* h) {
     auto* agg = (HashAgg*)h;
-    agg->ev_harvest_all();
+    agg->ring.harvest_all();
     agg->apply_launches = 0;
-    agg->apply_ms_total = 0;
+    agg->ring.ms_total = 0;
     agg->apply_rows = 0;
     agg->ev_seq = 0;
     return RW_OK;
@@ -5229,20 +5112,6 @@ __global__ void vnode_varlen_kernel(VnodeVarlenBatch b, int n_keys,
     }
 }
 
-// frees every device allocation of one call on any exit path
-struct DevAllocs {
-    std::vector<void*> ptrs;
-    ~DevAllocs() {
-        for (void* p : ptrs) hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T** out, size_t bytes) {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) ptrs.push_back(*out);
-        return e;
-    }
-};
-
 extern "C" {
 
 typedef struct {
@@ -5276,7 +5145,7 @@ static int vnode_compute_varlen(const RwVnodeDesc* d, const RwChunk* chunk,
         FAIL(RW_E_INVAL, "vnode_count %u (1..65536)", d->vnode_count);
     if (ensure_crc8_table() != RW_OK) FAIL(RW_E_INTERNAL, "crc table");
     if (n == 0) return RW_OK;
-    DevAllocs da;
+    DevOwner da;
     VnodeVarlenBatch b{};
     for (uint32_t k = 0; k < d->n_keys; k++) {
         const RwColumn& c = chunk->cols[d->key_indices[k]];
@@ -5290,7 +5159,7 @@ static int vnode_compute_varlen(const RwVnodeDesc* d, const RwChunk* chunk,
             uint32_t* offs;
             uint8_t* bytes;
             HIP_TRY(da.alloc(&offs, ((size_t)n + 1) * 4));
-            HIP_TRY(da.alloc(&bytes, vd->offsets[n]));
+            HIP_TRY(da.alloc(&bytes, vd->offsets[n] ? vd->offsets[n] : 1));
             HIP_TRY(hipMemcpy(offs, vd->offsets, ((size_t)n + 1) * 4,
                               hipMemcpyHostToDevice));
             if (vd->offsets[n])
@@ -5337,14 +5206,15 @@ int rw_vnode_compute(const RwVnodeDesc* d, const RwChunk* chunk, uint16_t* out) 
         if (chunk->cols[d->key_indices[k]].type == RW_T_VARCHAR)
             has_varchar = true;
     if (has_varchar) return vnode_compute_varlen(d, chunk, out);
+    DevOwner da;
     VnodeBatch b{};
     uint8_t types[4] = {0, 0, 0, 0};
     for (uint32_t k = 0; k < d->n_keys; k++) {
         const RwColumn& c = chunk->cols[d->key_indices[k]];
         types[k] = c.type;
         if (c.type == RW_T_BOOL) FAIL(RW_E_INVAL, "bool vnode key unsupported on GPU");
-        HIP_TRY(hipMalloc(&b.col_vals[k], (size_t)n * 8));
-        HIP_TRY(hipMalloc(&b.col_valid[k], n));
+        HIP_TRY(da.alloc(&b.col_vals[k], (size_t)n * 8));
+        HIP_TRY(da.alloc(&b.col_valid[k], n));
         if (c.type == RW_T_I32 || c.type == RW_T_F32) {
             // widen to i64 storage but hash native width
             std::vector<int64_t> tmp(n);
@@ -5360,7 +5230,7 @@ int rw_vnode_compute(const RwVnodeDesc* d, const RwChunk* chunk, uint16_t* out) 
     }
     b.n_rows = n;
     uint16_t* dout;
-    HIP_TRY(hipMalloc(&dout, (size_t)n * 2));
+    HIP_TRY(da.alloc(&dout, (size_t)n * 2));
     uint32_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (!blocks) blocks = 1;
@@ -5368,11 +5238,6 @@ int rw_vnode_compute(const RwVnodeDesc* d, const RwChunk* chunk, uint16_t* out) 
                                   types[0], types[1], types[2], types[3]);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 2, hipMemcpyDeviceToHost));
-    for (uint32_t k = 0; k < d->n_keys; k++) {
-        hipFree(b.col_vals[k]);
-        hipFree(b.col_valid[k]);
-    }
-    hipFree(dout);
     return RW_OK;
 }
 
@@ -7107,16 +6972,23 @@ __global__ void varlen_rewrite_kernel(JoinSideDev sd, int col, uint32_t n,
     }
 }
 
+int VarlenFetch::ensure_scan_tmp(size_t tmp) {
+    if (tmp <= d_scan_tmp_cap) return RW_OK;
+    d_scan_tmp_cap = 0;
+    HIP_TRY(mem.regrow(&d_scan_tmp, tmp));
+    d_scan_tmp_cap = tmp;
+    return RW_OK;
+}
+
 int VarlenFetch::ensure_vscratch(uint32_t n) {
     if (d_vcap >= n + 1) return RW_OK;
-    if (d_vlens) hipFree(d_vlens);
-    if (d_voffs) hipFree(d_voffs);
-    d_vlens = d_voffs = nullptr;
+    mem.release(&d_vlens);
+    mem.release(&d_voffs);
     d_vcap = 0;
     uint32_t cap = 4096;
     while (cap < n + 1) cap <<= 1;
-    HIP_TRY(hipMalloc(&d_vlens, (size_t)cap * 8));
-    HIP_TRY(hipMalloc(&d_voffs, (size_t)cap * 8));
+    HIP_TRY(mem.alloc(&d_vlens, (size_t)cap * 8));
+    HIP_TRY(mem.alloc(&d_voffs, (size_t)cap * 8));
     d_vcap = cap;
     return RW_OK;
 }
@@ -7146,13 +7018,8 @@ int VarlenFetch::fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
     HIP_TRY(rocprim::exclusive_scan(nullptr, tmp, d_vlens, d_voffs,
                                     (uint64_t)0, (size_t)n + 1,
                                     rocprim::plus<uint64_t>(), stream));
-    if (tmp > d_scan_tmp_cap) {
-        if (d_scan_tmp) hipFree(d_scan_tmp);
-        d_scan_tmp = nullptr;
-        d_scan_tmp_cap = 0;
-        HIP_TRY(hipMalloc(&d_scan_tmp, tmp));
-        d_scan_tmp_cap = tmp;
-    }
+    rc = ensure_scan_tmp(tmp);
+    if (rc != RW_OK) return rc;
     HIP_TRY(rocprim::exclusive_scan(d_scan_tmp, tmp, d_vlens, d_voffs,
                                     (uint64_t)0, (size_t)n + 1,
                                     rocprim::plus<uint64_t>(), stream));
@@ -7163,12 +7030,10 @@ int VarlenFetch::fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
     if (total) {
         uint64_t padded = total + VARLEN_COPY_PAD; // whole copy units
         if (d_vbytes_cap < padded) {
-            if (d_vbytes) hipFree(d_vbytes);
-            d_vbytes = nullptr;
             d_vbytes_cap = 0;
             uint64_t cap = 1ull << 16;
             while (cap < padded) cap <<= 1;
-            HIP_TRY(hipMalloc(&d_vbytes, cap));
+            HIP_TRY(mem.regrow(&d_vbytes, cap));
             d_vbytes_cap = cap;
         }
         if (timed) HIP_TRY(hipEventRecord(vev2, stream));
@@ -7197,10 +7062,6 @@ int VarlenFetch::fetch(const VarlenView& v, const uint8_t* arena, uint32_t n,
 }
 
 VarlenFetch::~VarlenFetch() {
-    if (d_vlens) hipFree(d_vlens);
-    if (d_voffs) hipFree(d_voffs);
-    if (d_vbytes) hipFree(d_vbytes);
-    if (d_scan_tmp) hipFree(d_scan_tmp);
     if (vev0) {
         hipEventDestroy(vev0);
         hipEventDestroy(vev1);
@@ -7213,7 +7074,8 @@ struct HashJoin {
     JoinMeta m{};
     JoinSideDev side[2]{};
     JoinOutDev out{};
-    hipStream_t stream;
+    hipStream_t stream = nullptr;
+    DevOwner mem; // every device buffer of this executor (rw_devmem.hpp)
     std::vector<uint8_t> out_types;
     std::vector<uint8_t> types[2];
     // staging
@@ -7237,27 +7099,8 @@ struct HashJoin {
     std::vector<uint8_t> ineq_larger, ineq_do_clean;
     std::vector<Wm> ineq_wm[2], ineq_out;
     // lazy event ring (same rationale as HashAgg: no per-step host sync)
-    static constexpr int EV_RING = 256;
-    hipEvent_t ev0[EV_RING] = {}, ev1[EV_RING] = {};
-    uint8_t ev_pending[EV_RING] = {};
-    uint64_t ev_head = 0;
-    double probe_ms_total = 0;
+    EventRing ring; // ring.ms_total: probe kernel time
     uint64_t probe_launches = 0, probe_rows = 0;
-
-    int ev_harvest(int slot) {
-        if (!ev_pending[slot]) return RW_OK;
-        HIP_TRY(hipEventSynchronize(ev1[slot]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0[slot], ev1[slot]));
-        probe_ms_total += ms;
-        ev_pending[slot] = 0;
-        return RW_OK;
-    }
-    int ev_harvest_all() {
-        for (int s = 0; s < EV_RING; s++)
-            if (ev_harvest(s) != RW_OK) return RW_E_INTERNAL;
-        return RW_OK;
-    }
 
     int init(const RwHashJoinDesc* d) {
         if (!gpu_ok()) FAIL(RW_E_NOGPU, "risingwave_amd: no GPU visible (product path has no CPU fallback)");
@@ -7409,7 +7252,7 @@ struct HashJoin {
             JoinSideDev& js = side[s];
             js.cap_mask = cap - 1;
             js.slots = nullptr; // join tables use compact 8-B slots
-            HIP_TRY(hipMalloc(&js.slots8, (size_t)cap * 8));
+            HIP_TRY(mem.alloc(&js.slots8, (size_t)cap * 8));
             HIP_TRY(hipMemsetAsync(js.slots8, 0, (size_t)cap * 8, stream));
             js.row_cap = (uint32_t)row_cap;
             uint32_t rs = 16 + 8 * (uint32_t)m.n_cols[s];
@@ -7419,51 +7262,42 @@ struct HashJoin {
             if (rs > 32 && rs <= 64) rs = 64;
             else if (rs > 64) rs = (rs + 31) & ~31u;
             js.row_stride = rs;
-            HIP_TRY(hipMalloc(&js.rows, (size_t)row_cap * js.row_stride));
-            HIP_TRY(hipMalloc(&js.row_cursor, 4));
+            HIP_TRY(mem.alloc(&js.rows, (size_t)row_cap * js.row_stride));
+            HIP_TRY(mem.alloc(&js.row_cursor, 4));
             HIP_TRY(hipMemset(js.row_cursor, 0, 4));
             // checkpoint-delta tracking (§8f-2)
             js.killed_cap = 1u << 22;
-            HIP_TRY(hipMalloc(&js.killed, (size_t)js.killed_cap * 4));
-            HIP_TRY(hipMalloc(&js.killed_cursor, 4));
+            HIP_TRY(mem.alloc(&js.killed, (size_t)js.killed_cap * 4));
+            HIP_TRY(mem.alloc(&js.killed_cursor, 4));
             HIP_TRY(hipMemset(js.killed_cursor, 0, 4));
             js.deg_dirty_flag = nullptr;
             js.deg_dirty_list = nullptr;
             js.deg_dirty_n = nullptr;
             if (m.need_deg[s]) {
-                HIP_TRY(hipMalloc(&js.deg_dirty_flag, (size_t)row_cap * 4));
+                HIP_TRY(mem.alloc(&js.deg_dirty_flag, (size_t)row_cap * 4));
                 HIP_TRY(hipMemset(js.deg_dirty_flag, 0, (size_t)row_cap * 4));
-                HIP_TRY(hipMalloc(&js.deg_dirty_list, (size_t)row_cap * 4));
-                HIP_TRY(hipMalloc(&js.deg_dirty_n, 4));
+                HIP_TRY(mem.alloc(&js.deg_dirty_list, (size_t)row_cap * 4));
+                HIP_TRY(mem.alloc(&js.deg_dirty_n, 4));
                 HIP_TRY(hipMemset(js.deg_dirty_n, 0, 4));
             }
         }
         HIP_TRY(hipStreamSynchronize(stream));
         out.cap = 1u << 22;
-        HIP_TRY(hipMalloc(&out.vals, (size_t)out.cap * m.n_out * 8));
-        HIP_TRY(hipMalloc(&out.nulls, (size_t)out.cap * m.n_out));
-        HIP_TRY(hipMalloc(&out.ops, out.cap));
-        HIP_TRY(hipMalloc(&out.counters, 8));
+        HIP_TRY(mem.alloc(&out.vals, (size_t)out.cap * m.n_out * 8));
+        HIP_TRY(mem.alloc(&out.nulls, (size_t)out.cap * m.n_out));
+        HIP_TRY(mem.alloc(&out.ops, out.cap));
+        HIP_TRY(mem.alloc(&out.counters, 8));
         HIP_TRY(hipMemset(out.counters, 0, 8));
         return RW_OK;
     }
 
     int ensure_stage(int s, uint32_t n) {
         if (stage_cap[s] >= n) return RW_OK;
-        for (int c = 0; c < m.n_cols[s]; c++) {
-            if (stage[s].col_vals[c]) hipFree(stage[s].col_vals[c]);
-            if (stage[s].col_valid[c]) hipFree(stage[s].col_valid[c]);
-        }
-        if (stage[s].ops) hipFree(stage[s].ops);
-        if (stage[s].vis) hipFree(stage[s].vis);
+        stage_cap[s] = 0;
         uint32_t cap = 4096;
         while (cap < n) cap <<= 1;
-        for (int c = 0; c < m.n_cols[s]; c++) {
-            HIP_TRY(hipMalloc(&stage[s].col_vals[c], (size_t)cap * 8));
-            HIP_TRY(hipMalloc(&stage[s].col_valid[c], cap));
-        }
-        HIP_TRY(hipMalloc(&stage[s].ops, cap));
-        HIP_TRY(hipMalloc(&stage[s].vis, cap));
+        int rc = stage_regrow(mem, stage[s], m.n_cols[s], cap, 8);
+        if (rc != RW_OK) return rc;
         stage_cap[s] = cap;
         return RW_OK;
     }
@@ -7492,17 +7326,9 @@ struct HashJoin {
         uint64_t cap = arena_cap[s] ? arena_cap[s]
                        : arena_reserve[s] ? arena_reserve[s] : ARENA_DEFAULT;
         while (cap < need) cap *= 2;
-        uint8_t* na = nullptr;
-        HIP_TRY(hipMalloc(&na, cap));
-        if (side[s].arena) {
-            // in-flight launches may still read the old buffer
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (arena_used[s])
-                HIP_TRY(hipMemcpy(na, side[s].arena, arena_used[s],
-                                  hipMemcpyDeviceToDevice));
-            hipFree(side[s].arena);
-        }
-        side[s].arena = na;
+        // in-flight launches may still read the old buffer
+        if (side[s].arena) HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(mem.regrow(&side[s].arena, cap, arena_used[s]));
         arena_cap[s] = cap;
         return RW_OK;
     }
@@ -7610,19 +7436,14 @@ struct HashJoin {
         if (!blocks) blocks = 1;
         int slot = -1;
         if (timed) {
-            slot = (int)(ev_head++ % EV_RING);
-            if (!ev0[slot]) {
-                HIP_TRY(hipEventCreate(&ev0[slot]));
-                HIP_TRY(hipEventCreate(&ev1[slot]));
-            }
-            if (ev_harvest(slot) != RW_OK) return RW_E_INTERNAL;
-            HIP_TRY(hipEventRecord(ev0[slot], stream));
+            slot = ring.begin(stream);
+            if (slot < 0) FAIL(RW_E_INTERNAL, "HIP event error (probe timing)");
         }
         if (m.join_type == RW_JOIN_INNER && !m.append_only && r0 == 0) {
             // pre-assigned sparse output + one-bump record reservation
             if (!d_probe_base) {
-                HIP_TRY(hipMalloc(&d_probe_base, 4));
-                HIP_TRY(hipMalloc(&d_emit_count, 8));
+                HIP_TRY(mem.alloc(&d_probe_base, 4));
+                HIP_TRY(mem.alloc(&d_emit_count, 8));
             }
             if (b.n_rows > out.cap)
                 FAIL(RW_E_INVAL, "probe batch larger than the output block");
@@ -7641,8 +7462,7 @@ struct HashJoin {
                 b, side[s], side[1 - s], m, s, out, r0, r1, d_probe_base);
         }
         if (timed) {
-            HIP_TRY(hipEventRecord(ev1[slot], stream));
-            ev_pending[slot] = 1;
+            HIP_TRY(ring.end(slot, stream));
             probe_launches++;
             probe_rows += b.n_rows;
         }
@@ -7704,8 +7524,9 @@ struct HashJoin {
         if (m.vc_mask[s] && cur > mark) {
             uint32_t nf = cur - mark;
             std::vector<uint64_t> words(nf);
+            DevOwner tmp;
             uint64_t* d_words = nullptr;
-            HIP_TRY(hipMalloc(&d_words, (size_t)nf * 8));
+            HIP_TRY(tmp.alloc(&d_words, (size_t)nf * 8));
             for (int c = 0; c < m.n_cols[s]; c++) {
                 if (!((m.vc_mask[s] >> c) & 1)) continue;
                 for (uint32_t i = 0; i < nf; i++) {
@@ -7715,21 +7536,15 @@ struct HashJoin {
                     words[i] = live ? ((const uint64_t*)(rec + 16))[c] : 0;
                 }
                 if (hipMemcpy(d_words, words.data(), (size_t)nf * 8,
-                              hipMemcpyHostToDevice) != hipSuccess) {
-                    hipFree(d_words);
+                              hipMemcpyHostToDevice) != hipSuccess)
                     FAIL(RW_E_INTERNAL, "drain string gather failed");
-                }
                 VarlenView v{};
                 v.words = d_words;
                 v.stride = 1;
                 int rcv = varlen_fetch(v, js.arena, nf, voffs[c], vbytes[c],
                                        false);
-                if (rcv != RW_OK) {
-                    hipFree(d_words);
-                    return rcv;
-                }
+                if (rcv != RW_OK) return rcv;
             }
-            hipFree(d_words);
         }
         auto encode_val = [&](const uint8_t* rec, std::vector<uint8_t>& v) {
             const uint32_t vb = ((const uint32_t*)rec)[2];
@@ -7772,8 +7587,9 @@ struct HashJoin {
         if (!old_ids.empty()) {
             uint32_t* d_ids = nullptr;
             uint8_t* d_out = nullptr;
-            HIP_TRY(hipMalloc(&d_ids, old_ids.size() * 4));
-            HIP_TRY(hipMalloc(&d_out, oldbuf.size()));
+            DevOwner tmp;
+            HIP_TRY(tmp.alloc(&d_ids, old_ids.size() * 4));
+            HIP_TRY(tmp.alloc(&d_out, oldbuf.size()));
             HIP_TRY(hipMemcpy(d_ids, old_ids.data(), old_ids.size() * 4,
                               hipMemcpyHostToDevice));
             uint32_t gblocks = ((uint32_t)old_ids.size() + 255) / 256;
@@ -7782,8 +7598,7 @@ struct HashJoin {
                 js, d_ids, (uint32_t)old_ids.size(), d_out);
             int rcg = hipMemcpy(oldbuf.data(), d_out, oldbuf.size(),
                                 hipMemcpyDeviceToHost);
-            hipFree(d_ids);
-            hipFree(d_out);
+            tmp.release_all();
             if (rcg != hipSuccess)
                 FAIL(RW_E_INTERNAL, "drain record gather failed");
         }
@@ -8293,45 +8108,7 @@ struct HashJoin {
     }
 
     ~HashJoin() {
-        for (int s = 0; s < EV_RING; s++)
-            if (ev0[s]) {
-                hipEventDestroy(ev0[s]);
-                hipEventDestroy(ev1[s]);
-            }
-        if (d_probe_base) {
-            hipFree(d_probe_base);
-            hipFree(d_emit_count);
-        }
-        if (d_vis_scratch) hipFree(d_vis_scratch);
-        for (int s = 0; s < 2; s++) {
-            if (compact_scratch[s]) hipFree(compact_scratch[s]);
-            if (side[s].arena) hipFree(side[s].arena);
-        }
-        for (int s = 0; s < 2; s++) {
-            JoinSideDev& js = side[s];
-            if (js.slots8) {
-                hipFree(js.slots8);
-                hipFree(js.rows);
-                hipFree(js.row_cursor);
-                if (js.killed) {
-                    hipFree(js.killed);
-                    hipFree(js.killed_cursor);
-                }
-            }
-            for (int c = 0; c < m.n_cols[s]; c++) {
-                if (stage[s].col_vals[c]) hipFree(stage[s].col_vals[c]);
-                if (stage[s].col_valid[c]) hipFree(stage[s].col_valid[c]);
-            }
-            if (stage[s].ops) hipFree(stage[s].ops);
-            if (stage[s].vis) hipFree(stage[s].vis);
-        }
-        if (out.vals) {
-            hipFree(out.vals);
-            hipFree(out.nulls);
-            hipFree(out.ops);
-            hipFree(out.counters);
-        }
-        if (zeros) hipFree(zeros);
+        mem.release_all(); // device memory goes before the stream
         if (stream) hipStreamDestroy(stream);
         for (auto* c : outq) rw_chunk_free(c);
     }
@@ -8383,11 +8160,8 @@ int rw_hash_join_varlen_reserve(void* h, int side, uint64_t bytes) {
         FAIL(RW_E_INVAL, "varlen_reserve is legal only before any input");
     if (!bytes || bytes > rwvarlen::MAX_OFF)
         FAIL(RW_E_INVAL, "varlen_reserve: bad capacity");
-    if (j->side[side].arena) {
-        hipFree(j->side[side].arena);
-        j->side[side].arena = nullptr;
-        j->arena_cap[side] = 0;
-    }
+    j->mem.release(&j->side[side].arena);
+    j->arena_cap[side] = 0;
     j->arena_reserve[side] = bytes;
     return j->arena_ensure(side, 0);
 }
@@ -8437,10 +8211,11 @@ int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
     // (state-table watermark range delete, state_table.rs:1707)
     uint32_t crec_cap = 1u << 18;
     for (;;) {
+        DevOwner tmp;
         DedupDirtyRec* crecs = nullptr;
         uint32_t* cmeta = nullptr; // [0]=n [1]=overflow
-        HIP_TRY(hipMalloc(&crecs, (size_t)crec_cap * sizeof(DedupDirtyRec)));
-        HIP_TRY(hipMalloc(&cmeta, 8));
+        HIP_TRY(tmp.alloc(&crecs, (size_t)crec_cap * sizeof(DedupDirtyRec)));
+        HIP_TRY(tmp.alloc(&cmeta, 8));
         HIP_TRY(hipMemset(cmeta, 0, 8));
         agg_clean_kernel<<<2048, 256, 0, agg->stream>>>(
             agg->t, (int)group_key_pos, val, agg->KW, agg->n_calls,
@@ -8463,8 +8238,7 @@ int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
         if (rcs == RW_OK && n && agg->has_vc())
             rcv = agg->fetch_key_strings((const uint64_t*)crecs,
                                          sizeof(DedupDirtyRec) / 8, n);
-        hipFree(crecs);
-        hipFree(cmeta);
+        tmp.release_all();
         if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "agg clean sync failed");
         if (rcv != RW_OK) return rcv;
         auto put32 = [&](uint32_t x) {
@@ -8507,7 +8281,7 @@ int rw_hash_agg_update_vnode_bitmap(void* h, const uint8_t* bitmap,
         FAIL(RW_E_INVAL, "vnode_count");
     if (ensure_crc_table() != RW_OK) FAIL(RW_E_INTERNAL, "crc table");
     if (!agg->d_vnode_bitmap)
-        HIP_TRY(hipMalloc(&agg->d_vnode_bitmap, 512));
+        HIP_TRY(agg->mem.alloc(&agg->d_vnode_bitmap, 512));
     HIP_TRY(hipMemcpyAsync(agg->d_vnode_bitmap, bitmap, vnode_count / 8,
                            hipMemcpyHostToDevice, agg->stream));
     uint8_t ty[4] = {RW_T_I64, RW_T_I64, RW_T_I64, RW_T_I64};
@@ -8527,7 +8301,7 @@ int rw_hash_join_update_vnode_bitmap(void* h, const uint8_t* bitmap,
     if (!vnode_count || vnode_count % 8 || vnode_count > 4096)
         FAIL(RW_E_INVAL, "vnode_count");
     if (ensure_crc_table() != RW_OK) FAIL(RW_E_INTERNAL, "crc table");
-    if (!j->d_vnode_bitmap) HIP_TRY(hipMalloc(&j->d_vnode_bitmap, 512));
+    if (!j->d_vnode_bitmap) HIP_TRY(j->mem.alloc(&j->d_vnode_bitmap, 512));
     HIP_TRY(hipMemcpyAsync(j->d_vnode_bitmap, bitmap, vnode_count / 8,
                            hipMemcpyHostToDevice, j->stream));
     for (int s = 0; s < 2; s++) {
@@ -8558,16 +8332,16 @@ void* rw_join_bench_preload(void* h, int side, const RwChunk* c) {
                 "varchar columns";
         return nullptr;
     }
-    auto* b = new JoinBatchDev{};
+    auto b = std::make_unique<Owned<JoinBatchDev>>();
     uint32_t n = c->n_rows;
     for (int ci = 0; ci < j->m.n_cols[side]; ci++) {
-        if (hipMalloc(&b->col_vals[ci], (size_t)n * 8) != hipSuccess) return nullptr;
-        if (hipMalloc(&b->col_valid[ci], n) != hipSuccess) return nullptr;
+        if (b->mem.alloc(&b->col_vals[ci], (size_t)n * 8) != hipSuccess) return nullptr;
+        if (b->mem.alloc(&b->col_valid[ci], n) != hipSuccess) return nullptr;
         hipMemcpy(b->col_vals[ci], c->cols[ci].data, (size_t)n * 8,
                   hipMemcpyHostToDevice);
         hipMemcpy(b->col_valid[ci], c->cols[ci].valid, n, hipMemcpyHostToDevice);
     }
-    if (hipMalloc(&b->ops, n) != hipSuccess) return nullptr;
+    if (b->mem.alloc(&b->ops, n) != hipSuccess) return nullptr;
     hipMemcpy(b->ops, c->ops, n, hipMemcpyHostToDevice);
     b->vis = nullptr;
     b->n_rows = n;
@@ -8580,7 +8354,7 @@ void* rw_join_bench_preload(void* h, int side, const RwChunk* c) {
         for (uint32_t r = 0; r < n && b->all_valid; r++)
             b->all_valid = c->cols[ci2].valid[r];
     b->unique_keys = 0;
-    return b;
+    return static_cast<JoinBatchDev*>(b.release());
 }
 
 // launch the probe for a preloaded batch; outputs accumulate in the device
@@ -8749,8 +8523,8 @@ int rw_join_vnode_hop(void* join_h, void* batch, uint32_t col, uint8_t type,
     auto* b = (JoinBatchDev*)batch;
     JOIN_NO_VARCHAR(j, "rw_join_vnode_hop");
     if (j->d_vnode_hop_cap < b->n_rows) {
-        if (j->d_vnode_hop) hipFree(j->d_vnode_hop);
-        HIP_TRY(hipMalloc(&j->d_vnode_hop, (size_t)b->n_rows * 2 + 2));
+        j->d_vnode_hop_cap = 0;
+        HIP_TRY(j->mem.regrow(&j->d_vnode_hop, (size_t)b->n_rows * 2 + 2));
         j->d_vnode_hop_cap = b->n_rows;
     }
     VnodeBatch vb{};
@@ -8780,7 +8554,7 @@ int rw_agg_apply_joinout(void* agg_h, void* join_h) {
     uint32_t n = ctr[0];
     if (!n) return RW_OK;
     if (!j->zeros) {
-        HIP_TRY(hipMalloc(&j->zeros, (size_t)j->out.cap * j->m.n_out));
+        HIP_TRY(j->mem.alloc(&j->zeros, (size_t)j->out.cap * j->m.n_out));
         HIP_TRY(hipMemset(j->zeros, 0, (size_t)j->out.cap * j->m.n_out));
     }
     AggBatch b{};
@@ -8818,8 +8592,8 @@ int rw_agg_apply_joinout(void* agg_h, void* join_h) {
     if (j->sparse_out) {
         // pre-assigned sparse output: sentinel rows masked by visibility
         if (j->d_vis_cap < n) {
-            if (j->d_vis_scratch) hipFree(j->d_vis_scratch);
-            HIP_TRY(hipMalloc(&j->d_vis_scratch, n));
+            j->d_vis_cap = 0;
+            HIP_TRY(j->mem.regrow(&j->d_vis_scratch, n));
             j->d_vis_cap = n;
         }
         uint32_t blocks = (n + 255) / 256;
@@ -8899,10 +8673,10 @@ int rw_q7pipe_bench_run(void* agg_h, void* join_h, void** agg_batches,
 
 int rw_join_kernel_stats(void* h, RwKernelStats* out) {
     auto* j = (HashJoin*)h;
-    if (j->ev_harvest_all() != RW_OK)
+    if (!j->ring.harvest_all())
         FAIL(RW_E_INTERNAL, "event harvest failed");
     out->launches = j->probe_launches;
-    out->total_ms = j->probe_ms_total;
+    out->total_ms = j->ring.ms_total;
     out->rows = j->probe_rows;
     return RW_OK;
 }
@@ -9040,8 +8814,9 @@ int rw_hash_join_restore(void* h, int side, const uint8_t* buf,
     }
     b.vis = nullptr;
     b.n_rows = n;
+    DevOwner tmp;
     uint32_t* ddeg = nullptr;
-    HIP_TRY(hipMalloc(&ddeg, (size_t)n * 4));
+    HIP_TRY(tmp.alloc(&ddeg, (size_t)n * 4));
     HIP_TRY(hipMemcpy(ddeg, degrees.data(), (size_t)n * 4,
                       hipMemcpyHostToDevice));
     uint32_t blocks = (n + 255) / 256;
@@ -9050,7 +8825,7 @@ int rw_hash_join_restore(void* h, int side, const uint8_t* buf,
         b, j->side[side], j->m, side, ddeg, j->out.counters + 1);
     int rcs = hipStreamSynchronize(j->stream) == hipSuccess ? RW_OK
                                                             : RW_E_INTERNAL;
-    hipFree(ddeg);
+    tmp.release(&ddeg);
     if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "restore sync failed");
     uint32_t ctr[2];
     HIP_TRY(hipMemcpy(ctr, j->out.counters, 8, hipMemcpyDeviceToHost));
@@ -9090,11 +8865,12 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
              cur - j->flush_mark[side]);
     if (cur > sd.row_cap) cur = sd.row_cap;
     if (!j->compact_scratch[side])
-        HIP_TRY(hipMalloc(&j->compact_scratch[side],
-                          (size_t)sd.row_cap * sd.row_stride));
+        HIP_TRY(j->mem.alloc(&j->compact_scratch[side],
+                             (size_t)sd.row_cap * sd.row_stride));
     uint8_t* nrows = j->compact_scratch[side];
+    DevOwner cur_mem;
     uint32_t* ncur = nullptr;
-    HIP_TRY(hipMalloc(&ncur, 4));
+    HIP_TRY(cur_mem.alloc(&ncur, 4));
     HIP_TRY(hipMemsetAsync(ncur, 0, 4, j->stream));
     jcompact_copy_kernel<<<4096, 256, 0, j->stream>>>(sd, nrows, ncur, cur);
     HIP_TRY(hipMemsetAsync(sd.slots8, 0,
@@ -9104,9 +8880,12 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
     uint32_t n_alive = 0;
     if (rcs == RW_OK)
         hipMemcpy(&n_alive, ncur, 4, hipMemcpyDeviceToHost);
-    hipFree(ncur);
+    cur_mem.release(&ncur);
     if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "compact copy failed");
-    j->compact_scratch[side] = sd.rows; // ping-pong
+    // ping-pong: both buffers are the same size and stay owned by j->mem,
+    // which tracks pointers, not slots — swapping the raw values needs no
+    // bookkeeping
+    j->compact_scratch[side] = sd.rows;
     sd.rows = nrows;
     HIP_TRY(hipMemcpy(sd.row_cursor, &n_alive, 4, hipMemcpyHostToDevice));
     jcompact_link_kernel<<<4096, 256, 0, j->stream>>>(sd, j->m, side,
@@ -9121,8 +8900,8 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
     uint64_t arena_freed = 0;
     if (j->m.vc_mask[side] && sd.arena) {
         uint8_t* na = nullptr;
-        HIP_TRY(hipMalloc(&na, j->arena_cap[side] +
-                               2 * VARLEN_COPY_PAD * MAX_COLS));
+        HIP_TRY(j->mem.alloc(&na, j->arena_cap[side] +
+                                  2 * VARLEN_COPY_PAD * MAX_COLS));
         uint64_t new_used = 0;
         int rcv = RW_OK;
         for (int c = 0; c < j->m.n_cols[side] && rcv == RW_OK && n_alive; c++) {
@@ -9144,15 +8923,9 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
                 rcv = RW_E_INTERNAL;
                 break;
             }
-            if (tmp > j->vf.d_scan_tmp_cap) {
-                if (j->vf.d_scan_tmp) hipFree(j->vf.d_scan_tmp);
-                j->vf.d_scan_tmp = nullptr;
-                j->vf.d_scan_tmp_cap = 0;
-                if (hipMalloc(&j->vf.d_scan_tmp, tmp) != hipSuccess) {
-                    rcv = RW_E_INTERNAL;
-                    break;
-                }
-                j->vf.d_scan_tmp_cap = tmp;
+            if (j->vf.ensure_scan_tmp(tmp) != RW_OK) {
+                rcv = RW_E_INTERNAL;
+                break;
             }
             uint64_t total = 0;
             if (rocprim::exclusive_scan(j->vf.d_scan_tmp, tmp, j->vf.d_vlens,
@@ -9186,10 +8959,10 @@ int rw_join_compact(void* h, int side, uint64_t* reclaimed) {
             new_used = base + total;
         }
         if (rcv != RW_OK) {
-            hipFree(na);
+            j->mem.release(&na);
             FAIL(RW_E_INTERNAL, "compact: arena rebuild failed");
         }
-        hipFree(sd.arena);
+        j->mem.release(&sd.arena);
         sd.arena = na;
         if (j->arena_used[side] > new_used)
             arena_freed = j->arena_used[side] - new_used;
@@ -9212,9 +8985,9 @@ int rw_join_degree_drain(void* h, int side, uint8_t** buf, uint64_t* len) {
 
 int rw_join_stats_reset(void* h) {
     auto* j = (HashJoin*)h;
-    j->ev_harvest_all();
+    j->ring.harvest_all();
     j->probe_launches = 0;
-    j->probe_ms_total = 0;
+    j->ring.ms_total = 0;
     j->probe_rows = 0;
     return RW_OK;
 }
@@ -9719,6 +9492,7 @@ struct GroupTopN {
     uint32_t* old_win = nullptr;
     uint32_t* old_n = nullptr;
     uint32_t old_cap = 0; // touched capacity for old_win/old_n
+    DevOwner mem; // every device buffer of this executor (rw_devmem.hpp)
     std::vector<uint8_t> types;
     std::vector<uint32_t> ck_col_idx;
     uint32_t chunk_size;
@@ -9781,89 +9555,51 @@ struct GroupTopN {
         sd.row_stride = 16 + 8u * (uint32_t)m.n_cols;
         sd.row_cap = (uint32_t)row_cap;
         HIP_TRY(hipStreamCreate(&stream));
-        HIP_TRY(hipMalloc(&sd.slots, cap * sizeof(JoinSlot)));
-        HIP_TRY(hipMalloc(&sd.rows, (size_t)row_cap * sd.row_stride));
-        HIP_TRY(hipMalloc(&sd.row_cursor, 4));
+        HIP_TRY(mem.alloc(&sd.slots, cap * sizeof(JoinSlot)));
+        HIP_TRY(mem.alloc(&sd.rows, (size_t)row_cap * sd.row_stride));
+        HIP_TRY(mem.alloc(&sd.row_cursor, 4));
         HIP_TRY(hipMemset(sd.row_cursor, 0, 4));
         sd.killed_cap = 1u << 22; // checkpoint-delta tracking (§8f-2)
-        HIP_TRY(hipMalloc(&sd.killed, (size_t)sd.killed_cap * 4));
-        HIP_TRY(hipMalloc(&sd.killed_cursor, 4));
+        HIP_TRY(mem.alloc(&sd.killed, (size_t)sd.killed_cap * 4));
+        HIP_TRY(mem.alloc(&sd.killed_cursor, 4));
         HIP_TRY(hipMemset(sd.killed_cursor, 0, 4));
-        HIP_TRY(hipMalloc(&touched, cap * 4));
+        HIP_TRY(mem.alloc(&touched, cap * 4));
         HIP_TRY(hipMemset(touched, 0, cap * 4));
-        HIP_TRY(hipMalloc(&tcounters, 8));
+        HIP_TRY(mem.alloc(&tcounters, 8));
         jslot_init_kernel<<<2048, 256, 0, stream>>>(sd.slots, cap);
         uint32_t out_cap = 1 << 18;
         out.cap = out_cap;
-        HIP_TRY(hipMalloc(&out.vals, (size_t)out_cap * m.n_cols * 8));
-        HIP_TRY(hipMalloc(&out.nulls, (size_t)out_cap * m.n_cols));
-        HIP_TRY(hipMalloc(&out.ops, out_cap));
-        HIP_TRY(hipMalloc(&out.counters, 8));
+        HIP_TRY(mem.alloc(&out.vals, (size_t)out_cap * m.n_cols * 8));
+        HIP_TRY(mem.alloc(&out.nulls, (size_t)out_cap * m.n_cols));
+        HIP_TRY(mem.alloc(&out.ops, out_cap));
+        HIP_TRY(mem.alloc(&out.counters, 8));
         HIP_TRY(hipMemset(out.counters, 0, 8));
         HIP_TRY(hipStreamSynchronize(stream));
         return RW_OK;
     }
 
     ~GroupTopN() {
-        if (sd.slots) {
-            hipFree(sd.slots);
-            hipFree(sd.rows);
-            hipFree(sd.row_cursor);
-            hipFree(sd.killed);
-            hipFree(sd.killed_cursor);
-            hipFree(touched);
-            hipFree(tcounters);
-            hipFree(out.vals);
-            hipFree(out.nulls);
-            hipFree(out.ops);
-            hipFree(out.counters);
-        }
-        if (touched_list) hipFree(touched_list);
-        if (old_win) hipFree(old_win);
-        if (compact_scratch) hipFree(compact_scratch);
-        free_stage();
+        mem.release_all(); // device memory goes before the stream
         if (stream) hipStreamDestroy(stream);
-        for (auto* c : outq) {
-            for (uint32_t i = 0; i < c->n_cols; i++) {
-                delete[] (int64_t*)c->cols[i].data;
-                delete[] (uint8_t*)c->cols[i].valid;
-            }
-            delete[] c->cols;
-            delete[] c->ops;
-            delete c;
-        }
-    }
-
-    void free_stage() {
-        if (!stage_cap) return;
-        for (int i = 0; i < m.n_cols; i++) {
-            hipFree(stage.col_vals[i]);
-            hipFree(stage.col_valid[i]);
-        }
-        hipFree(stage.ops);
-        hipFree(stage.vis);
-        stage_cap = 0;
+        for (auto* c : outq) rw_chunk_free(c);
     }
 
     int ensure_caps(uint32_t n) {
         if (stage_cap < n) {
-            free_stage();
-            for (int i = 0; i < m.n_cols; i++) {
-                HIP_TRY(hipMalloc(&stage.col_vals[i], (size_t)n * 8));
-                HIP_TRY(hipMalloc(&stage.col_valid[i], n));
-            }
-            HIP_TRY(hipMalloc(&stage.ops, n));
-            HIP_TRY(hipMalloc(&stage.vis, n));
+            stage_cap = 0;
+            int rc = stage_regrow(mem, stage, m.n_cols, n, 8);
+            if (rc != RW_OK) return rc;
             stage_cap = n;
         }
         if (old_cap < n) {
-            if (touched_list) hipFree(touched_list);
-            if (old_win) hipFree(old_win);
-            if (old_n) hipFree(old_n);
+            old_cap = 0;
+            mem.release(&touched_list);
+            mem.release(&old_win);
+            mem.release(&old_n);
             int K = m.with_ties ? TOPN_MAX_WIN : (int)(m.offset + m.limit);
-            HIP_TRY(hipMalloc(&touched_list, (size_t)n * 4));
-            HIP_TRY(hipMalloc(&old_win, (size_t)n * K * 4));
-            HIP_TRY(hipMalloc(&old_n, (size_t)n * 4));
+            HIP_TRY(mem.alloc(&touched_list, (size_t)n * 4));
+            HIP_TRY(mem.alloc(&old_win, (size_t)n * K * 4));
+            HIP_TRY(mem.alloc(&old_n, (size_t)n * 4));
             old_cap = n;
         }
         return RW_OK;
@@ -10031,10 +9767,11 @@ struct GroupTopN {
                              "(%u undrained fresh rows)", cur - flush_mark);
         if (cur > sd.row_cap) cur = sd.row_cap;
         if (!compact_scratch)
-            HIP_TRY(hipMalloc(&compact_scratch,
+            HIP_TRY(mem.alloc(&compact_scratch,
                               (size_t)sd.row_cap * sd.row_stride));
+        DevOwner tmp;
         uint32_t* ncur = nullptr;
-        HIP_TRY(hipMalloc(&ncur, 4));
+        HIP_TRY(tmp.alloc(&ncur, 4));
         HIP_TRY(hipMemsetAsync(ncur, 0, 4, stream));
         jcompact_copy_kernel<<<4096, 256, 0, stream>>>(sd, compact_scratch,
                                                        ncur, cur);
@@ -10045,11 +9782,11 @@ struct GroupTopN {
         uint32_t n_alive = 0;
         if (rcs == RW_OK)
             hipMemcpy(&n_alive, ncur, 4, hipMemcpyDeviceToHost);
-        hipFree(ncur);
+        tmp.release(&ncur);
         if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "topn compact copy failed");
-        uint8_t* old = sd.rows;
-        sd.rows = compact_scratch;
-        compact_scratch = old; // ping-pong
+        // ping-pong: both stay owned by `mem`, which tracks pointers and
+        // not slots, so swapping the raw values needs no bookkeeping
+        std::swap(sd.rows, compact_scratch);
         HIP_TRY(hipMemcpy(sd.row_cursor, &n_alive, 4,
                           hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(tcounters, 0, 8, stream));
@@ -10364,7 +10101,8 @@ extern "C" int rw_membw_rand_atomic(uint64_t bytes, int steps_per_thread,
                                     double* gops_out) {
     size_t n_lines = bytes / 64;
     unsigned long long* p = nullptr;
-    if (hipMalloc(&p, n_lines * 64) != hipSuccess) return RW_E_INTERNAL;
+    DevOwner tmp;
+    if (tmp.alloc(&p, n_lines * 64) != hipSuccess) return RW_E_INTERNAL;
     (void)hipMemset(p, 0, n_lines * 64);
     int grid = 2048, blk = 256;
     hipEvent_t e0, e1;
@@ -10378,7 +10116,7 @@ extern "C" int rw_membw_rand_atomic(uint64_t bytes, int steps_per_thread,
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     *gops_out = (double)grid * blk * steps_per_thread / (ms * 1e-3) / 1e9;
-    (void)hipFree(p);
+    tmp.release_all();
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return RW_OK;
@@ -10389,8 +10127,9 @@ extern "C" int rw_membw_rand_chase(uint64_t bytes, int steps, int mlp,
     size_t n_lines = bytes / 64;
     unsigned long long* p = nullptr;
     unsigned long long* sink = nullptr;
-    if (hipMalloc(&p, n_lines * 64) != hipSuccess) return RW_E_INTERNAL;
-    (void)hipMalloc(&sink, 8);
+    DevOwner tmp;
+    if (tmp.alloc(&p, n_lines * 64) != hipSuccess) return RW_E_INTERNAL;
+    (void)tmp.alloc(&sink, 8);
     (void)hipMemset(p, 1, n_lines * 64);
     int grid = 2048, blk = 256;
     hipEvent_t e0, e1;
@@ -10405,8 +10144,7 @@ extern "C" int rw_membw_rand_chase(uint64_t bytes, int steps, int mlp,
     (void)hipEventElapsedTime(&ms, e0, e1);
     *glines_out =
         (double)grid * blk * steps * mlp / (ms * 1e-3) / 1e9;
-    (void)hipFree(p);
-    (void)hipFree(sink);
+    tmp.release_all();
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return RW_OK;
@@ -10417,8 +10155,9 @@ extern "C" int rw_membw_rand_probe(uint64_t bytes, int steps_per_thread,
     size_t n_lines = bytes / 64;
     unsigned long long* p = nullptr;
     unsigned long long* sink = nullptr;
-    if (hipMalloc(&p, n_lines * 64) != hipSuccess) return RW_E_INTERNAL;
-    (void)hipMalloc(&sink, 8);
+    DevOwner tmp;
+    if (tmp.alloc(&p, n_lines * 64) != hipSuccess) return RW_E_INTERNAL;
+    (void)tmp.alloc(&sink, 8);
     (void)hipMemset(p, 1, n_lines * 64);
     int grid = 2048, blk = 256;
     hipEvent_t e0, e1;
@@ -10434,8 +10173,7 @@ extern "C" int rw_membw_rand_probe(uint64_t bytes, int steps_per_thread,
     double touches = (double)grid * blk * steps_per_thread;
     *glines_out = touches / (ms * 1e-3) / 1e9;
     *gbps_out = touches * 64 / (ms * 1e-3) / 1e9;
-    (void)hipFree(p);
-    (void)hipFree(sink);
+    tmp.release_all();
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return RW_OK;
@@ -10445,8 +10183,9 @@ extern "C" int rw_membw_probe(uint64_t bytes, int iters, double* gbps_out) {
     size_t n = bytes / sizeof(ulonglong2);
     ulonglong2* p = nullptr;
     unsigned long long* sink = nullptr;
-    if (hipMalloc(&p, n * sizeof(ulonglong2)) != hipSuccess) return RW_E_INTERNAL;
-    (void)hipMalloc(&sink, 8);
+    DevOwner tmp;
+    if (tmp.alloc(&p, n * sizeof(ulonglong2)) != hipSuccess) return RW_E_INTERNAL;
+    (void)tmp.alloc(&sink, 8);
     (void)hipMemset(p, 1, n * sizeof(ulonglong2));
     int grid = 8192; // ≫256 workgroups: fills all 8 XCDs
     hipEvent_t e0, e1;
@@ -10460,8 +10199,7 @@ extern "C" int rw_membw_probe(uint64_t bytes, int iters, double* gbps_out) {
     float ms = 0;
     (void)hipEventElapsedTime(&ms, e0, e1);
     *gbps_out = (double)bytes * iters / (ms * 1e-3) / 1e9;
-    (void)hipFree(p);
-    (void)hipFree(sink);
+    tmp.release_all();
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return RW_OK;

@@ -23,11 +23,13 @@
 #include <cstdlib>
 #include <ctime>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/rw_chunk.h"
 #include "../../include/rw_xpayload.hpp"
+#include "rw_devmem.hpp"
 
 static thread_local std::string g_xerr;
 
@@ -522,6 +524,7 @@ __global__ void xv_copy_kernel(XTBatch b, const uint32_t* dest_of_row,
 struct Exchange {
     ncclComm_t comm = nullptr;
     hipStream_t stream = nullptr;
+    DevOwner mem; // every device buffer of this context (rw_devmem.hpp)
     int rank = 0, n_ranks = 1;
     double exch_ms = 0;
     uint64_t exch_launches = 0;
@@ -592,30 +595,11 @@ void rw_exchange_destroy(void* h) {
     auto* x = (Exchange*)h;
     if (!x) return;
     if (x->comm) ncclCommDestroy(x->comm);
-    if (x->d_dest) hipFree(x->d_dest);
-    if (x->d_counts) {
-        hipFree(x->d_counts);
-        hipFree(x->d_offsets);
-        hipFree(x->d_count_mat);
-        hipFree(x->d_block_counts);
-        hipFree(x->d_block_bases);
-        hipEventDestroy(x->e0);
-        hipEventDestroy(x->e1);
-    }
-    if (x->t_dest) {
-        hipFree(x->t_dest);
-        hipFree(x->t_slot_src);
-    }
-    if (x->t_small) {
-        hipFree(x->t_block_counts);
-        hipFree(x->t_block_bases);
-        hipFree(x->t_block_vbytes);
-        hipFree(x->t_block_vbases);
-        hipFree(x->t_small);
-        hipFree(x->t_pair_send);
-        hipFree(x->t_pair_recv);
-        for (auto& e : x->t_ev) hipEventDestroy(e);
-    }
+    x->mem.release_all(); // device memory goes before the stream
+    if (x->e0) hipEventDestroy(x->e0);
+    if (x->e1) hipEventDestroy(x->e1);
+    for (auto& e : x->t_ev)
+        if (e) hipEventDestroy(e);
     if (x->stream) hipStreamDestroy(x->stream);
     delete x;
 }
@@ -644,16 +628,16 @@ int rw_exchange_run(void* h, const int64_t* const* col_vals,
     b.n_rows = n_rows;
 
     if (x->dest_cap < n_rows) {
-        if (x->d_dest) hipFree(x->d_dest);
-        XHIP(hipMalloc(&x->d_dest, (size_t)n_rows * 4));
+        x->dest_cap = 0;
+        XHIP(x->mem.regrow(&x->d_dest, (size_t)n_rows * 4));
         x->dest_cap = n_rows;
     }
     if (!x->d_counts) {
-        XHIP(hipMalloc(&x->d_counts, R * 8));
-        XHIP(hipMalloc(&x->d_offsets, R * 8));
-        XHIP(hipMalloc(&x->d_count_mat, R * 8));
-        XHIP(hipMalloc(&x->d_block_counts, (size_t)R * 2048 * 4));
-        XHIP(hipMalloc(&x->d_block_bases, (size_t)R * 2048 * 4));
+        XHIP(x->mem.alloc(&x->d_counts, R * 8));
+        XHIP(x->mem.alloc(&x->d_offsets, R * 8));
+        XHIP(x->mem.alloc(&x->d_count_mat, R * 8));
+        XHIP(x->mem.alloc(&x->d_block_counts, (size_t)R * 2048 * 4));
+        XHIP(x->mem.alloc(&x->d_block_bases, (size_t)R * 2048 * 4));
         XHIP(hipEventCreate(&x->e0));
         XHIP(hipEventCreate(&x->e1));
     }
@@ -846,27 +830,23 @@ static int partition_typed(Exchange* x, const RwXCol* cols, int n_cols,
 
     const int D = XMAX_DESTS;
     if (!x->t_small) {
-        XHIP(hipMalloc(&x->t_block_counts, (size_t)D * 2048 * 4));
-        XHIP(hipMalloc(&x->t_block_bases, (size_t)D * 2048 * 4));
-        XHIP(hipMalloc(&x->t_block_vbytes, (size_t)D * 2048 * 8));
-        XHIP(hipMalloc(&x->t_block_vbases, (size_t)D * 2048 * 8));
-        XHIP(hipMalloc(&x->t_pair_send, (size_t)D * 16));
-        XHIP(hipMalloc(&x->t_pair_recv, (size_t)D * 16));
+        XHIP(x->mem.alloc(&x->t_block_counts, (size_t)D * 2048 * 4));
+        XHIP(x->mem.alloc(&x->t_block_bases, (size_t)D * 2048 * 4));
+        XHIP(x->mem.alloc(&x->t_block_vbytes, (size_t)D * 2048 * 8));
+        XHIP(x->mem.alloc(&x->t_block_vbases, (size_t)D * 2048 * 8));
+        XHIP(x->mem.alloc(&x->t_pair_send, (size_t)D * 16));
+        XHIP(x->mem.alloc(&x->t_pair_recv, (size_t)D * 16));
         for (auto& e : x->t_ev) XHIP(hipEventCreate(&e));
-        XHIP(hipMalloc(&x->t_small, (size_t)4 * D * 8)); // last: the guard
+        XHIP(x->mem.alloc(&x->t_small, (size_t)4 * D * 8)); // last: the guard
     }
     if (x->t_cap < n_rows || !x->t_dest) {
-        if (x->t_dest) {
-            hipFree(x->t_dest);
-            hipFree(x->t_slot_src);
-            x->t_dest = x->t_slot_src = nullptr;
-            x->t_cap = 0;
-        }
+        x->mem.release(&x->t_dest);
+        x->mem.release(&x->t_slot_src);
+        x->t_cap = 0;
         size_t cap = n_rows ? n_rows : 1;
-        XHIP(hipMalloc(&x->t_dest, cap * 4));
-        if (hipMalloc(&x->t_slot_src, cap * 4) != hipSuccess) {
-            hipFree(x->t_dest);
-            x->t_dest = nullptr;
+        XHIP(x->mem.alloc(&x->t_dest, cap * 4));
+        if (x->mem.alloc(&x->t_slot_src, cap * 4) != hipSuccess) {
+            x->mem.release(&x->t_dest);
             XFAIL(-5, "HIP: out of memory (slot map)");
         }
         x->t_cap = (uint32_t)cap;
@@ -1104,12 +1084,26 @@ int rw_xbuf_read(void* host, const void* dev, uint64_t bytes) {
     return 0;
 }
 
+// Caller-owned buffers share one process-wide owner, never destroyed (a
+// static destructor would call into a HIP runtime that may be gone).
+static std::mutex g_xbuf_mu;
+static DevOwner& xbuf_mem() {
+    static DevOwner* o = new DevOwner();
+    return *o;
+}
 void* rw_xbuf_alloc(uint64_t bytes) {
+    std::lock_guard<std::mutex> lk(g_xbuf_mu);
     void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    (void)xbuf_mem().alloc(&p, bytes);
     return p;
 }
-void rw_xbuf_free(void* p) { hipFree(p); }
+void rw_xbuf_free(void* p) {
+    std::lock_guard<std::mutex> lk(g_xbuf_mu);
+    xbuf_mem().release(&p);
+}
+
+// debug/test only: device bytes this library's owners hold right now
+uint64_t rw_exchange_debug_dev_bytes_live(void) { return g_dev_bytes_live.load(); }
 
 int rw_exchange_stats(void* h, double* total_ms, uint64_t* launches) {
     auto* x = (Exchange*)h;

@@ -256,6 +256,15 @@ class Lib:
                 C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32]
         except AttributeError:
             pass
+        try:  # product library only: the oracle holds no device memory
+            L.rw_debug_dev_bytes_live.restype = C.c_uint64
+            L.rw_debug_dev_bytes_live.argtypes = []
+        except AttributeError:
+            pass
+
+    def dev_bytes_live(self):
+        """Device bytes the library's owners hold right now (exact)."""
+        return int(self.lib.rw_debug_dev_bytes_live())
 
     def last_error(self):
         return self.lib.rw_last_error().decode()
