@@ -384,7 +384,8 @@ int rw_hash_join_varlen_emit_stats(void* h, double* ms, double* copy_ms,
  * seen, once; each pushed batch is interned before the apply launch, so
  * the agg kernels key on words as they do for i64. The arena holds at most
  * 2^39 bytes (offset bit 39 marks a not-yet-interned word, rw_varlen.hpp).
- * Strings of groups that died are NOT reclaimed.
+ * Strings of groups that died stay in the arena and the table until
+ * rw_hash_agg_compact, which keeps the live groups' strings only.
  *  - Supported: varchar in any of the 1..4 group-key positions, mixed with
  *    i64/ts keys; count(*), count/sum/sum0 on i64/ts/decimal arguments
  *    (with retractions), append-only min/max.
@@ -437,6 +438,30 @@ int rw_hash_agg_varlen_intern_stats(void* h, double* kernel_ms,
  * contract: call after the drains; fails loudly on pending deltas. */
 int rw_agg_minput_compact(void* h, uint64_t* reclaimed);
 int rw_topn_compact(void* h, uint64_t* reclaimed);
+/* Key-table compaction for the HashAgg. Watermark cleaning,
+ * EOWC window close, vnode re-scoping and the flush's delete branch reset a
+ * group in place and keep its slot; this call gives those slots back, so a
+ * windowed plan sizes `state_capacity_hint` for the groups live at one time.
+ * On an executor with varchar group keys it also rebuilds the interning
+ * arena and table from the live groups' strings: a string held only by dead
+ * groups is gone, rw_hash_agg_varlen_stats reports the shrunken values.
+ * Same contract as the family: call between epochs, after the flush and the
+ * drains. Logical state, every later output (multiset and order), every
+ * later drain byte and every later restore are unchanged; the table
+ * capacity does not change. A dropped group that comes back is a freshly
+ * created one. `reclaimed` (optional) is the number of slots given back
+ * (0 when no group was dead; nothing moves then). RW_E_INVAL, with state
+ * untouched, when groups are dirty (pushed, not flushed), when ingest-mode
+ * rows are staged but not applied, or when a materialized-input table has
+ * undrained deltas. The DISTINCT dedup tables are keyed by (group, datum),
+ * not by slot, and stay as they are (rw_agg_dedup_drain nets cleaned rows).
+ * rw_hash_agg_state_stats reads the occupancy a binding decides on (any
+ * pointer may be NULL): compact when `slots_ready` nears `capacity`, after
+ * the checkpoint. */
+int rw_hash_agg_compact(void* h, uint64_t* reclaimed);        /* slots given back */
+int rw_hash_agg_state_stats(void* h, uint64_t* slots_ready,   /* READY slots      */
+                            uint64_t* groups_live,            /* of them, live    */
+                            uint64_t* capacity);              /* table slots      */
 int rw_topn_checkpoint_drain(void* h, uint8_t** buf, uint64_t* len);
 /* Replay concatenated rw_topn_checkpoint_drain streams into a freshly
  * created GroupTopN executor (PUT/DELETE frames net host-side; the

@@ -2391,6 +2391,200 @@ __global__ __launch_bounds__(256) void agg_intern_rehash_kernel(
     }
 }
 
+// ============ HashAgg key-table compaction ====================
+//
+// The clean / EOWC-close / vnode-rescope kernels and the flush's delete
+// branch reset a group in place and leave its slot READY, which keeps probe
+// clusters intact inside an epoch. Between epochs rw_hash_agg_compact gives
+// those slots back: live groups are packed into a temporary sized by their
+// number, the table is cleared to its as-created state, and the packed
+// groups are inserted again.
+//
+// A slot is LIVE when it is READY and has a persisted row (has_prev), a
+// pending change (dirty_flag) or a positive row count. The last term keeps
+// what an EOWC restore leaves: state with neither flag set.
+__device__ __forceinline__ bool agg_slot_live(const AggTableDev& t, size_t cap,
+                                              int row_count_index,
+                                              uint32_t slot) {
+    return t.has_prev[slot] || t.dirty_flag[slot] ||
+           t.acc[(size_t)row_count_index * cap + slot] > 0;
+}
+
+// out[0] = READY slots, out[1] = live ones; one atomic pair per wave
+__global__ __launch_bounds__(256) void agg_compact_count_kernel(
+    AggTableDev t, int row_count_index, unsigned long long* out) {
+    const size_t cap = (size_t)t.cap_mask + 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    uint32_t ready = 0, live = 0;
+    // wave-uniform trip count: the ballots below need every lane
+    for (size_t base = (size_t)blockIdx.x * blockDim.x; base < cap;
+         base += stride) {
+        size_t slot = base + threadIdx.x;
+        bool r = slot < cap && t.state[slot] == SLOT_READY;
+        bool l = r && agg_slot_live(t, cap, row_count_index, (uint32_t)slot);
+        ready += __popcll(__ballot(r));
+        live += __popcll(__ballot(l));
+    }
+    if (lane == 0 && ready) {
+        atomicAdd(&out[0], (unsigned long long)ready);
+        atomicAdd(&out[1], (unsigned long long)live);
+    }
+}
+
+// the packed temporary: n records, columns laid out as the table's are with
+// n in place of the capacity
+struct AggPackDev {
+    int64_t* keys;       // [n * KW]
+    uint32_t* key_nulls; // [n]
+    long long* acc;      // [n_calls][n]
+    uint8_t* has;        // [n_calls][n]
+    long long* prev;     // [n_calls][n]
+    uint8_t* prev_null;  // [n_calls][n]
+    long long* prev2;    // [n_calls][n], decimal executors
+    uint8_t* has_prev;   // [n]
+    unsigned long long* dsum; // [n_dec][4][n]
+    uint32_t* dscl;           // [n_dec][n]
+    long long* dspec;         // [n_dec][3][n]
+    uint32_t* mheads;    // [n_minput][n]
+    uint32_t* old_slot;  // [n]
+    uint32_t* new_slot;  // [n], minput executors
+    uint32_t* cursor;    // records packed so far
+    uint32_t* err;       // 1 = more live slots than counted, 2 = table full
+    uint32_t n;
+    int n_minput;
+};
+
+__global__ __launch_bounds__(256) void agg_compact_pack_kernel(
+    AggTableDev t, AggPackDev p, int KW, int n_calls, int row_count_index) {
+    const size_t cap = (size_t)t.cap_mask + 1;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    const uint64_t lanes_below = (1ull << lane) - 1;
+    const size_t n = p.n;
+    for (size_t base = (size_t)blockIdx.x * blockDim.x; base < cap;
+         base += stride) {
+        size_t slot = base + threadIdx.x;
+        bool live = slot < cap && t.state[slot] == SLOT_READY &&
+                    agg_slot_live(t, cap, row_count_index, (uint32_t)slot);
+        const uint64_t b = __ballot(live);
+        if (!b) continue; // wave-uniform
+        uint32_t wbase = 0;
+        if (lane == 0) wbase = atomicAdd(p.cursor, (uint32_t)__popcll(b));
+        wbase = __shfl(wbase, 0);
+        if (!live) continue;
+        size_t r = (size_t)wbase + __popcll(b & lanes_below);
+        if (r >= n) { // the count said otherwise: never write
+            atomicExch(p.err, 1u);
+            continue;
+        }
+        for (int k = 0; k < KW; k++) p.keys[r * KW + k] = t.keys[slot * KW + k];
+        p.key_nulls[r] = t.key_nulls[slot];
+        p.has_prev[r] = t.has_prev[slot];
+        p.old_slot[r] = (uint32_t)slot;
+        for (int ci = 0; ci < n_calls; ci++) {
+            p.acc[ci * n + r] = t.acc[ci * cap + slot];
+            p.has[ci * n + r] = t.has[ci * cap + slot];
+            p.prev[ci * n + r] = t.prev[ci * cap + slot];
+            p.prev_null[ci * n + r] = t.prev_null[ci * cap + slot];
+            if (t.prev2) p.prev2[ci * n + r] = t.prev2[ci * cap + slot];
+        }
+        for (int d = 0; d < t.n_dec; d++) {
+            for (int k = 0; k < 4; k++)
+                p.dsum[((size_t)d * 4 + k) * n + r] =
+                    t.dsum[((size_t)d * 4 + k) * cap + slot];
+            p.dscl[d * n + r] = t.dscl[d * cap + slot];
+            for (int k = 0; k < 3; k++)
+                p.dspec[((size_t)d * 3 + k) * n + r] =
+                    t.dspec[((size_t)d * 3 + k) * cap + slot];
+        }
+        for (int m = 0; m < p.n_minput; m++)
+            p.mheads[m * n + r] = t.mheads[m * cap + slot];
+    }
+}
+
+// varchar key words of the packed block -> provisional words over the OLD
+// arena (same offset, same length); word 0 (NULL) stays
+__global__ __launch_bounds__(256) void agg_compact_prov_kernel(
+    AggPackDev p, int KW, uint32_t vc_mask) {
+    const size_t total = (size_t)p.n * KW;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        if (!((vc_mask >> (i % KW)) & 1)) continue;
+        uint64_t w = (uint64_t)p.keys[i];
+        if (w)
+            p.keys[i] = (int64_t)rwvarlen::pack(
+                rwvarlen::PROV_BIT | rwvarlen::word_off(w),
+                rwvarlen::word_len(w));
+    }
+}
+
+// one lane per packed record, into the cleared table; the keys are distinct
+// and no more than the capacity, so a full table is an internal error
+__global__ __launch_bounds__(256) void agg_compact_reinsert_kernel(
+    AggTableDev t, AggPackDev p, int KW, int n_calls) {
+    const size_t cap = (size_t)t.cap_mask + 1;
+    const size_t n = p.n;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < n;
+         r += stride) {
+        int64_t kw[MAX_KW];
+        for (int k = 0; k < KW; k++) kw[k] = p.keys[r * KW + k];
+        uint32_t slot = table_find_or_insert(t.state, t.keys, t.key_nulls,
+                                             t.cap_mask, kw, p.key_nulls[r],
+                                             KW);
+        if (p.new_slot) p.new_slot[r] = slot;
+        if (slot == UINT32_MAX) {
+            atomicExch(p.err, 2u);
+            continue;
+        }
+        t.has_prev[slot] = p.has_prev[r];
+        t.dirty_flag[slot] = 0;
+        for (int ci = 0; ci < n_calls; ci++) {
+            t.acc[ci * cap + slot] = p.acc[ci * n + r];
+            t.has[ci * cap + slot] = p.has[ci * n + r];
+            t.prev[ci * cap + slot] = p.prev[ci * n + r];
+            t.prev_null[ci * cap + slot] = p.prev_null[ci * n + r];
+            if (t.prev2) t.prev2[ci * cap + slot] = p.prev2[ci * n + r];
+        }
+        for (int d = 0; d < t.n_dec; d++) {
+            for (int k = 0; k < 4; k++)
+                t.dsum[((size_t)d * 4 + k) * cap + slot] =
+                    p.dsum[((size_t)d * 4 + k) * n + r];
+            t.dscl[d * cap + slot] = p.dscl[d * n + r];
+            for (int k = 0; k < 3; k++)
+                t.dspec[((size_t)d * 3 + k) * cap + slot] =
+                    p.dspec[((size_t)d * 3 + k) * n + r];
+        }
+        for (int m = 0; m < p.n_minput; m++)
+            t.mheads[m * cap + slot] = p.mheads[m * n + r];
+    }
+}
+
+// materialized-input rows follow their group: one lane per (minput call,
+// packed record) walks the chain it moved and writes the new owner. The
+// store holds live rows only here (minput_compact ran first), and a chain
+// belongs to exactly one record, so no row is written twice.
+__global__ __launch_bounds__(256) void agg_compact_mslot_kernel(AggTableDev t,
+                                                                AggPackDev p) {
+    const size_t total = (size_t)p.n * p.n_minput;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        uint32_t slot = p.new_slot[i % p.n];
+        if (slot == UINT32_MAX) continue;
+        uint32_t row = p.mheads[i];
+        // a chain cannot be longer than the store: the bound ends a walk
+        // over a malformed chain
+        for (uint32_t steps = 0; row < t.mrow_cap && steps < t.mrow_cap;
+             steps++) {
+            t.mslot[row] = slot;
+            row = t.mnext[row];
+        }
+    }
+}
+
 struct HashAgg {
     RwHashAggDesc desc;
     std::vector<uint8_t> input_types;
@@ -4236,6 +4430,202 @@ struct HashAgg {
         return RW_OK;
     }
 
+    // ----- key-table compaction -----
+
+    // READY slots and the live groups among them; drains the stream
+    int state_counts(uint64_t* ready, uint64_t* live) {
+        DevOwner tmp;
+        unsigned long long* d = nullptr;
+        HIP_TRY(tmp.alloc(&d, 16));
+        HIP_TRY(hipMemsetAsync(d, 0, 16, stream));
+        agg_compact_count_kernel<<<grid_for(capacity), 256, 0, stream>>>(
+            t, (int)desc.row_count_index, d);
+        unsigned long long h[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        *ready = h[0];
+        *live = h[1];
+        return RW_OK;
+    }
+
+    // what a compaction must not run over: it would drop or reorder work
+    // the caller has not finished
+    int compact_refusals() {
+        if (erows)
+            FAIL(RW_E_INVAL, "agg compact: ingest-mode rows are staged but "
+                             "not applied (flush first)");
+        HIP_TRY(hipStreamSynchronize(stream));
+        uint32_t nd = 0;
+        HIP_TRY(hipMemcpy(&nd, t.counters, 4, hipMemcpyDeviceToHost));
+        if (nd)
+            FAIL(RW_E_INVAL, "agg compact: %u dirty groups are not flushed "
+                             "(call between epochs, after the flush)", nd);
+        if (n_minput) { // minput_compact's own check, before anything moves
+            uint32_t cur = 0, kcur = 0;
+            HIP_TRY(hipMemcpy(&cur, t.mcursor, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&kcur, t.mkilled_cursor, 4,
+                              hipMemcpyDeviceToHost));
+            for (int mi = 0; mi < n_minput; mi++) {
+                uint32_t fm = mi < (int)mflush_mark.size() ? mflush_mark[mi] : 0;
+                uint32_t km = mi < (int)mkill_mark.size() ? mkill_mark[mi] : 0;
+                if (fm != cur || km != kcur)
+                    FAIL(RW_E_INVAL, "agg compact requires drained minput "
+                                     "tables (table %d has undrained deltas)",
+                         mi);
+            }
+        }
+        return RW_OK;
+    }
+
+    // the table's per-slot arrays back to what init() leaves
+    int compact_clear() {
+        size_t cap = capacity;
+        HIP_TRY(hipMemsetAsync(t.state, 0, cap * 4, stream));
+        HIP_TRY(hipMemsetAsync(t.keys, 0, cap * KW * 8, stream));
+        HIP_TRY(hipMemsetAsync(t.key_nulls, 0, cap * 4, stream));
+        HIP_TRY(hipMemsetAsync(t.has, 0, cap * n_calls, stream));
+        HIP_TRY(hipMemsetAsync(t.prev, 0, cap * n_calls * 8, stream));
+        HIP_TRY(hipMemsetAsync(t.prev_null, 0, cap * n_calls, stream));
+        HIP_TRY(hipMemsetAsync(t.has_prev, 0, cap, stream));
+        HIP_TRY(hipMemsetAsync(t.dirty_flag, 0, cap * 4, stream));
+        if (n_dec) {
+            HIP_TRY(hipMemsetAsync(t.dsum, 0, (size_t)n_dec * 4 * cap * 8, stream));
+            HIP_TRY(hipMemsetAsync(t.dscl, 0, (size_t)n_dec * cap * 4, stream));
+            HIP_TRY(hipMemsetAsync(t.dspec, 0, (size_t)n_dec * 3 * cap * 8, stream));
+            HIP_TRY(hipMemsetAsync(t.prev2, 0, (size_t)n_calls * cap * 8, stream));
+        }
+        if (n_minput)
+            HIP_TRY(hipMemsetAsync(t.mheads, 0xFF, (size_t)n_minput * cap * 4,
+                                   stream));
+        // acc: the min / max identities
+        agg_init_kernel<<<2048, 256, 0, stream>>>(t, n_calls, cd(0), cd(1),
+                                                  cd(2), cd(3));
+        return RW_OK;
+    }
+
+    // Strings of dead groups: re-intern the packed block's varchar words
+    // into a fresh arena and table, reading the bytes from the old arena as
+    // a push reads them from its staging buffer (§17.2's rule holds: every
+    // byte hashed or compared was written before these launches).
+    int compact_reintern(const AggPackDev& p) {
+        uint64_t cells = (uint64_t)p.n * nv;
+        if (in_row_cap < cells) {
+            mem.release(&in.rowslot);
+            mem.release(&in.winners);
+            in_row_cap = 0;
+            uint64_t cap = 4096;
+            while (cap < cells) cap <<= 1;
+            HIP_TRY(mem.alloc(&in.rowslot, cap * 4));
+            HIP_TRY(mem.alloc(&in.winners, cap * 4));
+            in_row_cap = (uint32_t)(cap > UINT32_MAX ? UINT32_MAX : cap);
+        }
+        uint8_t* old_arena = in.arena;
+        uint64_t* old_slots = in.slots;
+        uint8_t* arena = nullptr;
+        uint64_t* slots = nullptr;
+        size_t tbytes = ((size_t)in.cap_mask + 1) * 8;
+        HIP_TRY(mem.alloc(&arena, in.arena_cap));
+        if (mem.alloc(&slots, tbytes) != hipSuccess) {
+            mem.release(&arena);
+            FAIL(RW_E_INTERNAL, "agg compact: intern table allocation failed");
+        }
+        // from here on the executor owns the new pair; the old pair is
+        // only read, as staging, until the stream drains
+        in.arena = arena;
+        in.slots = slots;
+        in.stg = old_arena;
+        unsigned long long t0 = rwvarlen::AGG_ARENA_HEADER;
+        HIP_TRY(hipMemsetAsync(arena, 0, rwvarlen::AGG_ARENA_HEADER, stream));
+        HIP_TRY(hipMemsetAsync(slots, 0, tbytes, stream));
+        HIP_TRY(hipMemcpy(in.tail, &t0, 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(in.ctr, 0, 8, stream));
+        agg_compact_prov_kernel<<<grid_for(p.n * (uint32_t)KW), 256, 0,
+                                  stream>>>(p, KW, vc_mask);
+        InternCols ic{};
+        for (int j = 0; j < nv; j++) ic.words[j] = p.keys + vpos[j];
+        ic.vis = nullptr;
+        ic.n_rows = p.n;
+        ic.nv = (uint32_t)nv;
+        ic.stride = (uint32_t)KW;
+        int rc = intern_run(ic);
+        if (rc != RW_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(stream)); // the old pair is done with
+        in.stg = in_stg;
+        mem.release(&old_arena);
+        mem.release(&old_slots);
+        return intern_sync_counts(); // exact tail / entries, pending bounds 0
+    }
+
+    int compact(uint64_t* reclaimed) {
+        if (reclaimed) *reclaimed = 0;
+        int rc = compact_refusals();
+        if (rc != RW_OK) return rc;
+        uint64_t ready = 0, live = 0;
+        rc = state_counts(&ready, &live);
+        if (rc != RW_OK) return rc;
+        if (live == ready) return RW_OK; // no dead group: nothing moves
+        if (n_minput) { // only live rows remain, heads rebuilt by owner
+            rc = minput_compact(nullptr);
+            if (rc != RW_OK) return rc;
+        }
+        // transient memory: the live groups' records, not the capacity
+        DevOwner tmp;
+        AggPackDev p{};
+        p.n = (uint32_t)live;
+        p.n_minput = n_minput;
+        size_t n = live ? live : 1, nc = n_calls;
+        HIP_TRY(tmp.alloc(&p.keys, n * KW * 8));
+        HIP_TRY(tmp.alloc(&p.key_nulls, n * 4));
+        HIP_TRY(tmp.alloc(&p.acc, nc * n * 8));
+        HIP_TRY(tmp.alloc(&p.has, nc * n));
+        HIP_TRY(tmp.alloc(&p.prev, nc * n * 8));
+        HIP_TRY(tmp.alloc(&p.prev_null, nc * n));
+        HIP_TRY(tmp.alloc(&p.has_prev, n));
+        HIP_TRY(tmp.alloc(&p.old_slot, n * 4));
+        if (n_dec) {
+            HIP_TRY(tmp.alloc(&p.prev2, nc * n * 8));
+            HIP_TRY(tmp.alloc(&p.dsum, (size_t)n_dec * 4 * n * 8));
+            HIP_TRY(tmp.alloc(&p.dscl, (size_t)n_dec * n * 4));
+            HIP_TRY(tmp.alloc(&p.dspec, (size_t)n_dec * 3 * n * 8));
+        }
+        if (n_minput) {
+            HIP_TRY(tmp.alloc(&p.mheads, (size_t)n_minput * n * 4));
+            HIP_TRY(tmp.alloc(&p.new_slot, n * 4));
+        }
+        HIP_TRY(tmp.alloc(&p.cursor, 8));
+        p.err = p.cursor + 1;
+        HIP_TRY(hipMemsetAsync(p.cursor, 0, 8, stream));
+        agg_compact_pack_kernel<<<grid_for(capacity), 256, 0, stream>>>(
+            t, p, KW, n_calls, (int)desc.row_count_index);
+        uint32_t ce[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(ce, p.cursor, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (ce[1] || ce[0] != p.n) // nothing has been changed yet
+            FAIL(RW_E_INTERNAL, "agg compact: packed %u of %u live groups",
+                 ce[0], p.n);
+        rc = compact_clear();
+        if (rc != RW_OK) return rc;
+        if (has_vc() && in_ready) {
+            rc = compact_reintern(p);
+            if (rc != RW_OK) return rc;
+        }
+        if (p.n) {
+            agg_compact_reinsert_kernel<<<grid_for(p.n), 256, 0, stream>>>(
+                t, p, KW, n_calls);
+            if (n_minput)
+                agg_compact_mslot_kernel<<<grid_for(p.n * (uint32_t)n_minput),
+                                           256, 0, stream>>>(t, p);
+        }
+        HIP_TRY(hipMemcpyAsync(ce, p.cursor, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (ce[1])
+            FAIL(RW_E_INTERNAL, "agg compact: reinsert found the table full");
+        rc = check_overflow(); // the intern pre-pass reports through counters[2]
+        if (rc != RW_OK) return rc;
+        if (reclaimed) *reclaimed = ready - live;
+        return RW_OK;
+    }
+
     // Host-side chunking with the U-pair no-split rule
     // (stream_chunk_builder.rs:188-218)
     void slice_outputs(const std::vector<long long>& vals,
@@ -4944,6 +5334,22 @@ int rw_agg_minput_restore(void* h, int mi, const uint8_t* buf, uint64_t len) {
 
 int rw_agg_minput_compact(void* h, uint64_t* reclaimed) {
     return ((HashAgg*)h)->minput_compact(reclaimed);
+}
+
+int rw_hash_agg_compact(void* h, uint64_t* reclaimed) {
+    return ((HashAgg*)h)->compact(reclaimed);
+}
+
+int rw_hash_agg_state_stats(void* h, uint64_t* slots_ready,
+                            uint64_t* groups_live, uint64_t* capacity) {
+    auto* agg = (HashAgg*)h;
+    uint64_t ready = 0, live = 0;
+    int rc = agg->state_counts(&ready, &live);
+    if (rc != RW_OK) return rc;
+    if (slots_ready) *slots_ready = ready;
+    if (groups_live) *groups_live = live;
+    if (capacity) *capacity = agg->capacity;
+    return RW_OK;
 }
 
 int rw_agg_n_dedup_tables(void* h) {
