@@ -18,8 +18,12 @@
 // (secs, nanos) — byte-compatible restore into real Hummock needs that form
 // (a later-round item, noted in DESIGN.md).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <map>
+#include <optional>
+#include <string>
 #include <vector>
 
 #include "rw_chunk.h"
@@ -310,6 +314,90 @@ inline bool for_each_frame(const uint8_t* buf, uint64_t len, F&& fn) {
         off += 5 + (uint64_t)klen + 4 + vlen;
     }
     return off == len;
+}
+
+typedef std::vector<uint8_t> Bytes;
+
+// append one spill frame; a DELETE is put == 0 with vlen == 0
+inline void put_frame(Bytes& out, uint8_t put, const uint8_t* key,
+                      size_t klen, const uint8_t* val, size_t vlen) {
+    auto put32 = [&](uint32_t x) {
+        for (int b = 0; b < 4; b++) out.push_back((uint8_t)(x >> (8 * b)));
+    };
+    out.push_back(put);
+    put32((uint32_t)klen);
+    out.insert(out.end(), key, key + klen);
+    put32((uint32_t)vlen);
+    out.insert(out.end(), val, val + vlen);
+}
+inline void put_frame(Bytes& out, uint8_t put, const Bytes& key,
+                      const Bytes& val = {}) {
+    put_frame(out, put, key.data(), key.size(), val.data(), val.size());
+}
+
+// replay a frame stream into `m`: a PUT assigns, a DELETE erases (last write
+// wins, as a KV store compaction would); false on a malformed stream
+typedef std::map<std::string, Bytes> FrameMap;
+inline bool merge_frames(const uint8_t* buf, uint64_t len, FrameMap& m) {
+    return for_each_frame(buf, len,
+                          [&](uint8_t put, const uint8_t* k, uint32_t klen,
+                              const uint8_t* v, uint32_t vlen) {
+                              std::string key((const char*)k, klen);
+                              if (put)
+                                  m[key].assign(v, v + vlen);
+                              else
+                                  m.erase(key);
+                          });
+}
+
+// cursor over one value-encoded row; each read returns false on a cut or
+// unknown datum and never looks past len
+struct RowReader {
+    const uint8_t* p;
+    size_t len;
+    size_t off = 0;
+
+    bool datum(uint8_t type, DatumC* d) {
+        size_t got = value_decode_datum(p + off, len - off, type, d);
+        off += got;
+        return got != 0;
+    }
+    bool str(bool* null, const uint8_t** s, uint32_t* n) {
+        size_t got = value_decode_str(p + off, len - off, null, s, n);
+        off += got;
+        return got != 0;
+    }
+};
+
+// One epoch's delta of a state table whose keys net host-side: the last
+// put/del of a key wins, write() emits the frames in bytewise key order.
+class KeyedDelta {
+    std::map<Bytes, std::optional<Bytes>> m_;
+
+public:
+    void put(Bytes key, Bytes val) { m_[std::move(key)] = std::move(val); }
+    void del(Bytes key) { m_[std::move(key)] = std::nullopt; }
+    void write(Bytes& out) const {
+        for (auto& [k, v] : m_)
+            if (v)
+                put_frame(out, 1, k, *v);
+            else
+                put_frame(out, 0, k);
+    }
+};
+
+// Records that are collected first and ordered after: stable, so a PUT and a
+// DELETE under one key leave in the order they were added.
+struct FrameRec {
+    uint8_t put;
+    Bytes k, v;
+};
+inline void write_sorted(Bytes& out, std::vector<FrameRec>& rs) {
+    std::stable_sort(rs.begin(), rs.end(),
+                     [](const FrameRec& a, const FrameRec& b) {
+                         return a.k < b.k;
+                     });
+    for (auto& e : rs) put_frame(out, e.put, e.k, e.v);
 }
 
 } // namespace rwcodec

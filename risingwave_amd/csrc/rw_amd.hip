@@ -27,7 +27,6 @@
 #include <map>
 #include <memory>
 #include <new>
-#include <optional>
 #include <string>
 #include <unordered_set>
 #include <vector>
@@ -403,6 +402,19 @@ struct JoinRowHdr {
     uint32_t next;
     uint32_t validbits; // bit c = column c non-NULL
     uint32_t degree;    // matches on the other side (outer/semi/anti types)
+};
+
+// host view of one row record copied off the device (the checkpoint drains)
+struct HostRow {
+    const uint8_t* rec;
+    const JoinRowHdr& hdr() const { return *(const JoinRowHdr*)rec; }
+    const int64_t* words() const {
+        return (const int64_t*)(rec + sizeof(JoinRowHdr));
+    }
+    bool null(int c) const { return !((hdr().validbits >> c) & 1); }
+    rwcodec::DatumC datum(uint8_t type, int c) const {
+        return rwcodec::datum_of_word(type, null(c), words()[c]);
+    }
 };
 
 struct JoinSideDev {
@@ -3829,20 +3841,15 @@ struct HashAgg {
     void spill_records_eowc(const std::vector<long long>& vals,
                             const std::vector<uint8_t>& nulls,
                             uint32_t n_out) {
-        auto put32 = [&](uint32_t x) {
-            for (int b = 0; b < 4; b++) spill.push_back((uint8_t)(x >> (8 * b)));
-        };
+        std::vector<uint8_t> k;
         for (uint32_t r = 0; r < n_out; r++) {
-            spill.push_back(0);
-            std::vector<uint8_t> k;
+            k.clear();
             for (int i = 0; i < KW; i++) {
                 rwcodec::DatumC d{nulls[(size_t)r * out_width + i] != 0,
                                   vals[(size_t)r * out_width + i], 0};
                 rwcodec::memcmp_encode_datum(k, out_types[i], d, {});
             }
-            put32((uint32_t)k.size());
-            spill.insert(spill.end(), k.begin(), k.end());
-            put32(0);
+            rwcodec::put_frame(spill, 0, k);
         }
     }
 
@@ -3856,15 +3863,13 @@ struct HashAgg {
                        const std::vector<uint8_t>& nulls,
                        const std::vector<uint8_t>& ops, uint32_t n_out,
                        const std::vector<long long>& vals2 = {}) {
-        auto put32 = [&](uint32_t x) {
-            for (int b = 0; b < 4; b++) spill.push_back((uint8_t)(x >> (8 * b)));
-        };
+        std::vector<uint8_t> k, v;
         for (uint32_t r = 0; r < n_out; r++) {
             uint8_t op = ops[r];
             if (op == RW_OP_UPDATE_DELETE) continue;
             uint8_t put = op != RW_OP_DELETE;
-            spill.push_back(put);
-            std::vector<uint8_t> k, v;
+            k.clear();
+            v.clear();
             for (int i = 0; i < KW; i++)
                 encode_key_datum(k, true, i, r,
                                  nulls[(size_t)r * out_width + i] != 0,
@@ -3887,10 +3892,7 @@ struct HashAgg {
                     }
                 }
             }
-            put32((uint32_t)k.size());
-            spill.insert(spill.end(), k.begin(), k.end());
-            put32((uint32_t)v.size());
-            spill.insert(spill.end(), v.begin(), v.end());
+            rwcodec::put_frame(spill, put, k, v);
         }
     }
 
@@ -3931,13 +3933,12 @@ struct HashAgg {
                                        out_types.begin() + KW);
         key_types.push_back(distinct_col_types[di]);
         auto& persisted = dedup_persisted[di];
-        struct Rec { std::vector<uint8_t> k, v; uint8_t put; };
-        std::vector<Rec> rs;
+        std::vector<rwcodec::FrameRec> rs;
         rs.reserve(n);
         for (uint32_t i = 0; i < n; i++) {
             const DedupDirtyRec& r = recs[i];
             uint32_t slot = slots_h[i];
-            Rec e;
+            rwcodec::FrameRec e;
             // signed view: a retract of a never-inserted datum wraps the u32
             // below 0 — match the oracle's signed-count semantics (the
             // reference's count is i64; inconsistent input tolerance)
@@ -3967,18 +3968,8 @@ struct HashAgg {
             }
             rs.push_back(std::move(e));
         }
-        std::sort(rs.begin(), rs.end(),
-                  [](const Rec& a, const Rec& b) { return a.k < b.k; });
-        auto put32 = [&](uint32_t x) {
-            for (int b = 0; b < 4; b++) out.push_back((uint8_t)(x >> (8 * b)));
-        };
-        for (auto& e : rs) {
-            out.push_back(e.put);
-            put32((uint32_t)e.k.size());
-            out.insert(out.end(), e.k.begin(), e.k.end());
-            put32((uint32_t)e.v.size());
-            out.insert(out.end(), e.v.begin(), e.v.end());
-        }
+        // keys are distinct here: one slot is one (group, datum)
+        rwcodec::write_sorted(out, rs);
         return RW_OK;
     }
 
@@ -3993,18 +3984,9 @@ struct HashAgg {
                  distinct_slots.size());
         int rc = ensure_dedup(1);
         if (rc != RW_OK) return rc;
-        std::map<std::string, std::vector<uint8_t>> merged;
-        bool ok = rwcodec::for_each_frame(
-            buf, len,
-            [&](uint8_t put, const uint8_t* k, uint32_t klen,
-                const uint8_t* v, uint32_t vlen) {
-                std::string key((const char*)k, klen);
-                if (put)
-                    merged[key].assign(v, v + vlen);
-                else
-                    merged.erase(key);
-            });
-        if (!ok) FAIL(RW_E_INVAL, "malformed spill stream");
+        rwcodec::FrameMap merged;
+        if (!rwcodec::merge_frames(buf, len, merged))
+            FAIL(RW_E_INVAL, "malformed spill stream");
         uint32_t n = (uint32_t)merged.size();
         if (!n) return RW_OK;
         int KW1 = KW + 1;
@@ -4016,21 +3998,16 @@ struct HashAgg {
         uint32_t i = 0;
         for (auto& [kbytes, val] : merged) {
             (void)kbytes;
-            size_t off = 0;
+            rwcodec::RowReader rd{val.data(), val.size()};
+            rwcodec::DatumC d;
             for (int c = 0; c < KW1; c++) {
-                rwcodec::DatumC d;
-                size_t got = rwcodec::value_decode_datum(
-                    val.data() + off, val.size() - off, key_types[c], &d);
-                if (!got) FAIL(RW_E_INVAL, "dedup restore: bad key datum");
-                off += got;
+                if (!rd.datum(key_types[c], &d))
+                    FAIL(RW_E_INVAL, "dedup restore: bad key datum");
                 keys[(size_t)i * KW1 + c] =
                     d.null ? 0 : rwcodec::word_of_datum(key_types[c], d);
                 nulls[i] |= (uint32_t)(d.null != 0) << c;
             }
-            rwcodec::DatumC d;
-            size_t got = rwcodec::value_decode_datum(
-                val.data() + off, val.size() - off, RW_T_I64, &d);
-            if (!got || d.null)
+            if (!rd.datum(RW_T_I64, &d) || d.null)
                 FAIL(RW_E_INVAL, "dedup restore: bad count datum");
             counts[i] = (uint32_t)d.i;
             i++;
@@ -4039,17 +4016,11 @@ struct HashAgg {
         uint32_t *dnulls = nullptr, *dcounts = nullptr, *dslots_out = nullptr,
                  *derr = nullptr;
         DevOwner tmp;
-        HIP_TRY(tmp.alloc(&dkeys, keys.size() * 8));
-        HIP_TRY(tmp.alloc(&dnulls, (size_t)n * 4));
-        HIP_TRY(tmp.alloc(&dcounts, (size_t)n * 4));
+        HIP_TRY(tmp.upload(&dkeys, keys));
+        HIP_TRY(tmp.upload(&dnulls, nulls));
+        HIP_TRY(tmp.upload(&dcounts, counts));
         HIP_TRY(tmp.alloc(&dslots_out, (size_t)n * 4));
         HIP_TRY(tmp.alloc(&derr, 4));
-        HIP_TRY(hipMemcpy(dkeys, keys.data(), keys.size() * 8,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dnulls, nulls.data(), (size_t)n * 4,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dcounts, counts.data(), (size_t)n * 4,
-                          hipMemcpyHostToDevice));
         HIP_TRY(hipMemset(derr, 0, 4));
         dedup_restore_kernel<<<grid_for(n), 256, 0, stream>>>(
             dkeys, dnulls, dcounts, n, KW1, dedup_slots[di], dedup_cap_mask,
@@ -4138,9 +4109,8 @@ struct HashAgg {
                 break;
             }
         }
-        auto encode = [&](uint32_t row, std::string* k,
+        auto encode = [&](uint32_t row, std::vector<uint8_t>& kb,
                           std::vector<uint8_t>* v) {
-            std::vector<uint8_t> kb;
             uint32_t slot = mslot_h[row];
             for (int i2 = 0; i2 < KW; i2++) {
                 rwcodec::DatumC d{((gnulls[slot] >> i2) & 1) != 0,
@@ -4158,7 +4128,6 @@ struct HashAgg {
                 rwcodec::memcmp_encode_datum(
                     kb, input_types[stream_key[k2]], d, {});
             }
-            k->assign((const char*)kb.data(), kb.size());
             if (v) {
                 for (int i2 = 0; i2 < KW; i2++) {
                     rwcodec::DatumC d{((gnulls[slot] >> i2) & 1) != 0,
@@ -4177,40 +4146,24 @@ struct HashAgg {
                 }
             }
         };
-        struct Rec {
-            std::string k;
-            std::vector<uint8_t> v;
-            uint8_t put;
-        };
-        std::vector<Rec> rs;
+        std::vector<rwcodec::FrameRec> rs;
         for (uint32_t row = mflush_mark[mi]; row < cur; row++) {
             if (mc[row] != (uint8_t)mi || !alive[row]) continue;
-            Rec e;
-            e.put = 1;
-            encode(row, &e.k, &e.v);
+            rwcodec::FrameRec e{1, {}, {}};
+            encode(row, e.k, &e.v);
             rs.push_back(std::move(e));
         }
         for (uint32_t i2 = mkill_mark[mi]; i2 < kcur; i2++) {
             uint32_t row = kills[i2];
             if (row >= cur || mc[row] != (uint8_t)mi) continue;
             if (row >= mflush_mark[mi]) continue; // created+died this epoch
-            Rec e;
-            e.put = 0;
-            encode(row, &e.k, nullptr);
+            rwcodec::FrameRec e{0, {}, {}};
+            encode(row, e.k, nullptr);
             rs.push_back(std::move(e));
         }
-        std::stable_sort(rs.begin(), rs.end(),
-                         [](const Rec& a, const Rec& b) { return a.k < b.k; });
-        auto put32 = [&](uint32_t x) {
-            for (int b = 0; b < 4; b++) out.push_back((uint8_t)(x >> (8 * b)));
-        };
-        for (auto& e : rs) {
-            out.push_back(e.put);
-            put32((uint32_t)e.k.size());
-            out.insert(out.end(), e.k.begin(), e.k.end());
-            put32((uint32_t)e.v.size());
-            out.insert(out.end(), e.v.begin(), e.v.end());
-        }
+        // a PUT and a DELETE can share a key here: the stable order keeps
+        // the PUT first
+        rwcodec::write_sorted(out, rs);
         mflush_mark[mi] = cur;
         mkill_mark[mi] = kcur;
         return RW_OK;
@@ -4331,18 +4284,9 @@ struct HashAgg {
                 break;
             }
         }
-        std::map<std::string, std::vector<uint8_t>> merged;
-        bool ok = rwcodec::for_each_frame(
-            buf, len,
-            [&](uint8_t put, const uint8_t* k, uint32_t klen,
-                const uint8_t* v, uint32_t vlen) {
-                std::string key((const char*)k, klen);
-                if (put)
-                    merged[key].assign(v, v + vlen);
-                else
-                    merged.erase(key);
-            });
-        if (!ok) FAIL(RW_E_INVAL, "malformed minput spill stream");
+        rwcodec::FrameMap merged;
+        if (!rwcodec::merge_frames(buf, len, merged))
+            FAIL(RW_E_INVAL, "malformed minput spill stream");
         uint32_t n = (uint32_t)merged.size();
         if (!n) return RW_OK;
         std::vector<int64_t> gk((size_t)n * KW);
@@ -4354,20 +4298,17 @@ struct HashAgg {
         uint32_t i2 = 0;
         for (auto& [kb, val] : merged) {
             (void)kb;
-            size_t off = 0;
+            rwcodec::RowReader row{val.data(), val.size()};
             auto rd = [&](uint8_t ty, long long* vv, uint8_t* nn) -> bool {
                 rwcodec::DatumC d;
-                size_t got = rwcodec::value_decode_datum(
-                    val.data() + off, val.size() - off, ty, &d);
-                if (!got) return false;
-                off += got;
+                if (!row.datum(ty, &d)) return false;
                 *vv = d.null ? 0 : rwcodec::word_of_datum(ty, d);
                 *nn = d.null;
                 return true;
             };
+            long long vv;
+            uint8_t nn;
             for (int k2 = 0; k2 < KW; k2++) {
-                long long vv;
-                uint8_t nn;
                 if (!rd(out_types[k2], &vv, &nn))
                     FAIL(RW_E_INVAL, "minput restore: bad group datum");
                 gk[(size_t)i2 * KW + k2] = vv;
@@ -4376,8 +4317,6 @@ struct HashAgg {
             if (!rd(input_types[calls[ci].arg], &mv[i2], &mn[i2]))
                 FAIL(RW_E_INVAL, "minput restore: bad value datum");
             for (int k2 = 0; k2 < t.n_sk; k2++) {
-                long long vv;
-                uint8_t nn;
                 if (!rd(input_types[stream_key[k2]], &vv, &nn))
                     FAIL(RW_E_INVAL, "minput restore: bad stream-key datum");
                 sks[(size_t)k2 * n + i2] = vv;
@@ -4389,28 +4328,15 @@ struct HashAgg {
         uint32_t* dgn = nullptr;
         long long* dmv = nullptr;
         uint8_t* dmn = nullptr;
-        long long* dsk = nullptr;
+        long long* dsk = nullptr; // the two stay null without stream keys
         uint8_t* dskn = nullptr;
         DevOwner tmp;
-        HIP_TRY(tmp.alloc(&dgk, gk.size() * 8));
-        HIP_TRY(tmp.alloc(&dgn, gn.size() * 4));
-        HIP_TRY(tmp.alloc(&dmv, mv.size() * 8));
-        HIP_TRY(tmp.alloc(&dmn, mn.size()));
-        HIP_TRY(tmp.alloc(&dsk, sks.size() * 8 + 8));
-        HIP_TRY(tmp.alloc(&dskn, skns.size() + 1));
-        HIP_TRY(hipMemcpy(dgk, gk.data(), gk.size() * 8,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dgn, gn.data(), gn.size() * 4,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dmv, mv.data(), mv.size() * 8,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dmn, mn.data(), mn.size(), hipMemcpyHostToDevice));
-        if (!sks.empty()) {
-            HIP_TRY(hipMemcpy(dsk, sks.data(), sks.size() * 8,
-                              hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(dskn, skns.data(), skns.size(),
-                              hipMemcpyHostToDevice));
-        }
+        HIP_TRY(tmp.upload(&dgk, gk));
+        HIP_TRY(tmp.upload(&dgn, gn));
+        HIP_TRY(tmp.upload(&dmv, mv));
+        HIP_TRY(tmp.upload(&dmn, mn));
+        HIP_TRY(tmp.upload(&dsk, sks));
+        HIP_TRY(tmp.upload(&dskn, skns));
         agg_minput_restore_kernel<<<grid_for(n), 256, 0, stream>>>(
             t, KW, mi, dgk, dgn, dmv, dmn, dsk, dskn, n);
         int rc2 = hipStreamSynchronize(stream) == hipSuccess ? RW_OK
@@ -4428,6 +4354,102 @@ struct HashAgg {
         HIP_TRY(hipMemcpy(&cur, t.mcursor, 4, hipMemcpyDeviceToHost));
         for (int j = 0; j < n_minput; j++) mflush_mark[j] = cur;
         return RW_OK;
+    }
+
+    // §8f-5 recovery of the result table. minput-bearing executors:
+    // minput_restore must run for every minput table BEFORE this call (prev
+    // outputs are recomputed from the hydrated chains, mirroring
+    // agg_group.rs:219-221)
+    int restore(const uint8_t* buf, uint64_t len) {
+        rwcodec::FrameMap merged;
+        if (!rwcodec::merge_frames(buf, len, merged))
+            FAIL(RW_E_INVAL, "malformed spill stream");
+        uint32_t n = (uint32_t)merged.size();
+        if (!n) return RW_OK;
+        int nc = n_calls;
+        std::vector<int64_t> keys((size_t)n * KW);
+        std::vector<uint32_t> knulls(n, 0);
+        std::vector<long long> vals((size_t)nc * n);
+        std::vector<uint8_t> vnulls((size_t)nc * n);
+        std::vector<long long> vals2;
+        if (n_dec) vals2.assign((size_t)nc * n, 0);
+        // varchar group keys: the decoded strings are packed into one host
+        // buffer and take the same staging + intern path a pushed chunk does
+        std::vector<uint8_t> sbytes;
+        uint32_t i = 0;
+        for (auto& [kbytes, val] : merged) {
+            (void)kbytes;
+            rwcodec::RowReader rd{val.data(), val.size()};
+            for (int c = 0; c < KW + nc; c++) {
+                uint8_t ty = out_types[c];
+                if (c < KW && ((vc_mask >> c) & 1)) {
+                    bool null = false;
+                    const uint8_t* s = nullptr;
+                    uint32_t slen = 0;
+                    if (!rd.str(&null, &s, &slen) || slen > rwvarlen::MAX_LEN)
+                        FAIL(RW_E_INVAL, "restore: bad varchar key datum");
+                    keys[(size_t)i * KW + c] =
+                        null ? 0
+                             : (int64_t)rwvarlen::pack(
+                                   rwvarlen::PROV_BIT | (uint64_t)sbytes.size(),
+                                   slen);
+                    knulls[i] |= (uint32_t)null << c;
+                    if (!null) sbytes.insert(sbytes.end(), s, s + slen);
+                    continue;
+                }
+                rwcodec::DatumC d;
+                if (!rd.datum(ty, &d))
+                    FAIL(RW_E_INVAL, "restore: bad state datum");
+                if (c < KW) {
+                    keys[(size_t)i * KW + c] = d.null ? 0 : d.i;
+                    knulls[i] |= (uint32_t)(d.null != 0) << c;
+                } else {
+                    vals[(size_t)(c - KW) * n + i] =
+                        rwcodec::word_of_datum(ty, d);
+                    vnulls[(size_t)(c - KW) * n + i] = d.null;
+                    if (n_dec) vals2[(size_t)(c - KW) * n + i] = d.i2;
+                }
+            }
+            i++;
+        }
+        int64_t* dkeys = nullptr;
+        uint32_t* dknulls = nullptr;
+        long long* dvals = nullptr;
+        uint8_t* dvnulls = nullptr;
+        long long* dvals2 = nullptr; // stays null without decimal calls
+        DevOwner tmp;
+        HIP_TRY(tmp.upload(&dkeys, keys));
+        HIP_TRY(tmp.upload(&dknulls, knulls));
+        HIP_TRY(tmp.upload(&dvals, vals));
+        HIP_TRY(tmp.upload(&dvnulls, vnulls));
+        HIP_TRY(tmp.upload(&dvals2, vals2));
+        if (has_vc()) {
+            int rcv = intern_prepare((uint64_t)n * nv, sbytes.size());
+            if (rcv == RW_OK && !sbytes.empty() &&
+                hipMemcpy(in_stg, sbytes.data(), sbytes.size(),
+                          hipMemcpyHostToDevice) != hipSuccess) {
+                g_err = "restore: staging copy failed";
+                rcv = RW_E_INTERNAL;
+            }
+            if (rcv == RW_OK) {
+                InternCols ic{};
+                for (int j = 0; j < nv; j++) ic.words[j] = dkeys + vpos[j];
+                ic.vis = nullptr;
+                ic.n_rows = n;
+                ic.nv = (uint32_t)nv;
+                ic.stride = (uint32_t)KW;
+                rcv = intern_run(ic);
+            }
+            if (rcv != RW_OK) return rcv;
+        }
+        agg_restore_kernel<<<grid_for(n), 256, 0, stream>>>(
+            t, KW, nc, dkeys, dknulls, dvals, dvnulls, dvals2, n,
+            eowc ? 0 : 1, cd(0), cd(1), cd(2), cd(3));
+        int rc = hipStreamSynchronize(stream) == hipSuccess ? RW_OK
+                                                            : RW_E_INTERNAL;
+        tmp.release_all();
+        if (rc != RW_OK) FAIL(RW_E_INTERNAL, "restore sync failed");
+        return check_overflow();
     }
 
     // ----- key-table compaction -----
@@ -5198,126 +5220,7 @@ int rw_agg_checkpoint_drain(void* h, uint8_t** buf, uint64_t* len) {
 }
 
 int rw_hash_agg_restore(void* h, const uint8_t* buf, uint64_t len) {
-    auto* agg = (HashAgg*)h;
-    // minput-bearing executors: rw_agg_minput_restore must run for every
-    // minput table BEFORE this call (prev outputs are recomputed from the
-    // hydrated chains, mirroring agg_group.rs:219-221)
-    std::map<std::string, std::vector<uint8_t>> merged;
-    bool ok = rwcodec::for_each_frame(
-        buf, len,
-        [&](uint8_t put, const uint8_t* k, uint32_t klen, const uint8_t* v,
-            uint32_t vlen) {
-            std::string key((const char*)k, klen);
-            if (put)
-                merged[key].assign(v, v + vlen);
-            else
-                merged.erase(key);
-        });
-    if (!ok) FAIL(RW_E_INVAL, "malformed spill stream");
-    uint32_t n = (uint32_t)merged.size();
-    if (!n) return RW_OK;
-    int KW = agg->KW, nc = agg->n_calls;
-    std::vector<int64_t> keys((size_t)n * KW);
-    std::vector<uint32_t> knulls(n, 0);
-    std::vector<long long> vals((size_t)nc * n);
-    std::vector<uint8_t> vnulls((size_t)nc * n);
-    std::vector<long long> vals2;
-    if (agg->n_dec) vals2.assign((size_t)nc * n, 0);
-    // varchar group keys: the decoded strings are packed into one host
-    // buffer and take the same staging + intern path a pushed chunk does
-    std::vector<uint8_t> sbytes;
-    uint32_t i = 0;
-    for (auto& [kbytes, val] : merged) {
-        (void)kbytes;
-        size_t off = 0;
-        for (int c = 0; c < KW + nc; c++) {
-            rwcodec::DatumC d;
-            uint8_t ty = agg->out_types[c];
-            if (c < KW && ((agg->vc_mask >> c) & 1)) {
-                bool null = false;
-                const uint8_t* s = nullptr;
-                uint32_t slen = 0;
-                size_t gots = rwcodec::value_decode_str(
-                    val.data() + off, val.size() - off, &null, &s, &slen);
-                if (!gots || slen > rwvarlen::MAX_LEN)
-                    FAIL(RW_E_INVAL, "restore: bad varchar key datum");
-                off += gots;
-                keys[(size_t)i * KW + c] =
-                    null ? 0
-                         : (int64_t)rwvarlen::pack(
-                               rwvarlen::PROV_BIT | (uint64_t)sbytes.size(),
-                               slen);
-                knulls[i] |= (uint32_t)null << c;
-                if (!null) sbytes.insert(sbytes.end(), s, s + slen);
-                continue;
-            }
-            size_t got = rwcodec::value_decode_datum(val.data() + off,
-                                                     val.size() - off, ty, &d);
-            if (!got) FAIL(RW_E_INVAL, "restore: bad state datum");
-            off += got;
-            if (c < KW) {
-                keys[(size_t)i * KW + c] = d.null ? 0 : d.i;
-                knulls[i] |= (uint32_t)(d.null != 0) << c;
-            } else {
-                vals[(size_t)(c - KW) * n + i] =
-                    rwcodec::word_of_datum(ty, d);
-                vnulls[(size_t)(c - KW) * n + i] = d.null;
-                if (agg->n_dec) vals2[(size_t)(c - KW) * n + i] = d.i2;
-            }
-        }
-        i++;
-    }
-    int64_t* dkeys = nullptr;
-    uint32_t* dknulls = nullptr;
-    long long* dvals = nullptr;
-    uint8_t* dvnulls = nullptr;
-    long long* dvals2 = nullptr;
-    DevOwner tmp;
-    HIP_TRY(tmp.alloc(&dkeys, keys.size() * 8));
-    HIP_TRY(tmp.alloc(&dknulls, knulls.size() * 4));
-    HIP_TRY(tmp.alloc(&dvals, vals.size() * 8));
-    HIP_TRY(tmp.alloc(&dvnulls, vnulls.size()));
-    HIP_TRY(hipMemcpy(dkeys, keys.data(), keys.size() * 8,
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dknulls, knulls.data(), knulls.size() * 4,
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dvals, vals.data(), vals.size() * 8,
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dvnulls, vnulls.data(), vnulls.size(),
-                      hipMemcpyHostToDevice));
-    if (agg->n_dec) {
-        HIP_TRY(tmp.alloc(&dvals2, vals2.size() * 8));
-        HIP_TRY(hipMemcpy(dvals2, vals2.data(), vals2.size() * 8,
-                          hipMemcpyHostToDevice));
-    }
-    if (agg->has_vc()) {
-        int rcv = agg->intern_prepare((uint64_t)n * agg->nv, sbytes.size());
-        if (rcv == RW_OK && !sbytes.empty() &&
-            hipMemcpy(agg->in_stg, sbytes.data(), sbytes.size(),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            g_err = "restore: staging copy failed";
-            rcv = RW_E_INTERNAL;
-        }
-        if (rcv == RW_OK) {
-            InternCols ic{};
-            for (int j = 0; j < agg->nv; j++)
-                ic.words[j] = dkeys + agg->vpos[j];
-            ic.vis = nullptr;
-            ic.n_rows = n;
-            ic.nv = (uint32_t)agg->nv;
-            ic.stride = (uint32_t)KW;
-            rcv = agg->intern_run(ic);
-        }
-        if (rcv != RW_OK) return rcv;
-    }
-    agg_restore_kernel<<<agg->grid_for(n), 256, 0, agg->stream>>>(
-        agg->t, KW, nc, dkeys, dknulls, dvals, dvnulls, dvals2, n,
-        agg->eowc ? 0 : 1, agg->cd(0), agg->cd(1), agg->cd(2), agg->cd(3));
-    int rc = hipStreamSynchronize(agg->stream) == hipSuccess ? RW_OK
-                                                             : RW_E_INTERNAL;
-    tmp.release_all();
-    if (rc != RW_OK) FAIL(RW_E_INTERNAL, "restore sync failed");
-    return agg->check_overflow();
+    return ((HashAgg*)h)->restore(buf, len);
 }
 
 int rw_agg_n_minput_tables(void* h) { return ((HashAgg*)h)->n_minput; }
@@ -7909,17 +7812,15 @@ struct HashJoin {
         if (kcur)
             HIP_TRY(hipMemcpy(kills.data(), js.killed, (size_t)kcur * 4,
                               hipMemcpyDeviceToHost));
-        auto encode_key = [&](const uint8_t* rec, std::string& k) {
-            const uint32_t vb = ((const uint32_t*)rec)[2]; // validbits
-            const int64_t* vals = (const int64_t*)(rec + 16);
-            std::vector<uint8_t> kb;
+        auto encode_key = [&](HostRow row) {
+            std::vector<uint8_t> k;
             auto put_datum = [&](uint8_t col) {
-                rwcodec::DatumC d{!((vb >> col) & 1), vals[col], 0};
-                rwcodec::memcmp_encode_datum(kb, types[s][col], d, {});
+                rwcodec::memcmp_encode_datum(
+                    k, types[s][col], row.datum(types[s][col], col), {});
             };
             for (int i = 0; i < m.KW; i++) put_datum(m.key_cols[s][i]);
             for (int i = 0; i < m.n_pk[s]; i++) put_datum(m.pk_cols[s][i]);
-            k.assign((const char*)kb.data(), kb.size());
+            return k;
         };
         // varchar cells of the fresh records: fetch their strings with the
         // emit path's gather kernels (one strided view per column over the
@@ -7936,10 +7837,9 @@ struct HashJoin {
             for (int c = 0; c < m.n_cols[s]; c++) {
                 if (!((m.vc_mask[s] >> c) & 1)) continue;
                 for (uint32_t i = 0; i < nf; i++) {
-                    const uint8_t* rec = fresh.data() + (size_t)i * stride;
-                    const uint32_t* hd = (const uint32_t*)rec;
-                    bool live = hd[0] && ((hd[2] >> c) & 1);
-                    words[i] = live ? ((const uint64_t*)(rec + 16))[c] : 0;
+                    HostRow row{fresh.data() + (size_t)i * stride};
+                    bool live = row.hdr().alive && !row.null(c);
+                    words[i] = live ? (uint64_t)row.words()[c] : 0;
                 }
                 if (hipMemcpy(d_words, words.data(), (size_t)nf * 8,
                               hipMemcpyHostToDevice) != hipSuccess)
@@ -7952,22 +7852,22 @@ struct HashJoin {
                 if (rcv != RW_OK) return rcv;
             }
         }
-        auto encode_val = [&](const uint8_t* rec, std::vector<uint8_t>& v) {
-            const uint32_t vb = ((const uint32_t*)rec)[2];
-            const int64_t* vals = (const int64_t*)(rec + 16);
+        auto encode_val = [&](HostRow row) {
+            std::vector<uint8_t> v;
             for (int c = 0; c < m.n_cols[s]; c++) {
                 if ((m.vc_mask[s] >> c) & 1) {
                     // only fresh records are value-encoded (PUT frames)
-                    size_t i = (size_t)(rec - fresh.data()) / stride;
+                    size_t i = (size_t)(row.rec - fresh.data()) / stride;
                     uint64_t o0 = voffs[c][i], o1 = voffs[c][i + 1];
-                    rwcodec::value_encode_str(v, !((vb >> c) & 1),
+                    rwcodec::value_encode_str(v, row.null(c),
                                               vbytes[c].data() + o0,
                                               (uint32_t)(o1 - o0));
                     continue;
                 }
-                rwcodec::DatumC d{!((vb >> c) & 1), vals[c], 0};
-                rwcodec::value_encode_datum(v, types[s][c], d);
+                rwcodec::value_encode_datum(v, types[s][c],
+                                            row.datum(types[s][c], c));
             }
+            return v;
         };
         // batched gather of every pre-epoch record the kill and degree-
         // dirty lists reference (single kernel + one D2H copy)
@@ -7994,10 +7894,8 @@ struct HashJoin {
             uint32_t* d_ids = nullptr;
             uint8_t* d_out = nullptr;
             DevOwner tmp;
-            HIP_TRY(tmp.alloc(&d_ids, old_ids.size() * 4));
+            HIP_TRY(tmp.upload(&d_ids, old_ids));
             HIP_TRY(tmp.alloc(&d_out, oldbuf.size()));
-            HIP_TRY(hipMemcpy(d_ids, old_ids.data(), old_ids.size() * 4,
-                              hipMemcpyHostToDevice));
             uint32_t gblocks = ((uint32_t)old_ids.size() + 255) / 256;
             if (gblocks > 2048) gblocks = 2048;
             jgather_rows_kernel<<<gblocks, 256, 0, stream>>>(
@@ -8008,31 +7906,15 @@ struct HashJoin {
             if (rcg != hipSuccess)
                 FAIL(RW_E_INTERNAL, "drain record gather failed");
         }
-        std::map<std::string, std::optional<std::vector<uint8_t>>> delta;
-        for (size_t i = 0; i < n_kill_old; i++) {
-            std::string k;
-            encode_key(oldbuf.data() + i * stride, k);
-            delta[k] = std::nullopt; // DELETE (a later PUT overwrites = net)
-        }
+        rwcodec::KeyedDelta delta;
+        for (size_t i = 0; i < n_kill_old; i++) // a later PUT overwrites = net
+            delta.del(encode_key({oldbuf.data() + i * stride}));
         for (uint32_t i = mark; i < cur; i++) {
-            const uint8_t* rec = fresh.data() + (size_t)(i - mark) * stride;
-            if (!((const uint32_t*)rec)[0]) continue; // dead: netted away
-            std::string k;
-            encode_key(rec, k);
-            std::vector<uint8_t> v;
-            encode_val(rec, v);
-            delta[k] = std::move(v);
+            HostRow row{fresh.data() + (size_t)(i - mark) * stride};
+            if (!row.hdr().alive) continue; // dead: netted away
+            delta.put(encode_key(row), encode_val(row));
         }
-        auto put32 = [&](uint32_t x) {
-            for (int b = 0; b < 4; b++) sp.push_back((uint8_t)(x >> (8 * b)));
-        };
-        for (auto& [k, v] : delta) {
-            sp.push_back(v.has_value() ? 1 : 0);
-            put32((uint32_t)k.size());
-            sp.insert(sp.end(), k.begin(), k.end());
-            put32(v ? (uint32_t)v->size() : 0);
-            if (v) sp.insert(sp.end(), v->begin(), v->end());
-        }
+        delta.write(sp);
         // §8f-2 degree-table deltas (build_degree_row, join/row.rs:99-113:
         // pk = jk ∥ pk as the main table, value = order key ++ degree i64).
         // Keys mirror the main delta (a degree row exists iff its state row
@@ -8040,64 +7922,171 @@ struct HashJoin {
         // (deg_dirty list). Serialized into deg_spill[s], returned by
         // rw_join_degree_drain after this drain.
         if (m.need_deg[s]) {
-            auto encode_deg_val = [&](const uint8_t* rec,
-                                      std::vector<uint8_t>& v) {
-                const uint32_t vb = ((const uint32_t*)rec)[2];
-                const int64_t* vals = (const int64_t*)(rec + 16);
+            auto encode_deg_val = [&](HostRow row) {
+                std::vector<uint8_t> v;
                 auto put_datum = [&](uint8_t col) {
-                    rwcodec::DatumC d{!((vb >> col) & 1), vals[col], 0};
-                    rwcodec::value_encode_datum(v, types[s][col], d);
+                    rwcodec::value_encode_datum(
+                        v, types[s][col], row.datum(types[s][col], col));
                 };
                 for (int i = 0; i < m.KW; i++) put_datum(m.key_cols[s][i]);
                 for (int i = 0; i < m.n_pk[s]; i++) put_datum(m.pk_cols[s][i]);
-                uint32_t deg = ((const uint32_t*)rec)[3];
-                rwcodec::value_encode_datum(v, RW_T_I64,
-                                            {false, (long long)deg, 0});
+                rwcodec::value_encode_datum(
+                    v, RW_T_I64, {false, (long long)row.hdr().degree, 0});
+                return v;
             };
-            std::map<std::string, std::optional<std::vector<uint8_t>>> dd;
-            for (size_t i = 0; i < n_kill_old; i++) {
-                std::string k;
-                encode_key(oldbuf.data() + i * stride, k);
-                dd[k] = std::nullopt;
-            }
+            rwcodec::KeyedDelta dd;
+            for (size_t i = 0; i < n_kill_old; i++)
+                dd.del(encode_key({oldbuf.data() + i * stride}));
             for (uint32_t i = mark; i < cur; i++) {
-                const uint8_t* rec = fresh.data() + (size_t)(i - mark) * stride;
-                if (!((const uint32_t*)rec)[0]) continue;
-                std::string k;
-                encode_key(rec, k);
-                std::vector<uint8_t> v;
-                encode_deg_val(rec, v);
-                dd[k] = std::move(v);
+                HostRow row{fresh.data() + (size_t)(i - mark) * stride};
+                if (row.hdr().alive) dd.put(encode_key(row), encode_deg_val(row));
             }
             // pre-epoch rows whose degree changed (gathered above after
-            // the kill entries)
+            // the kill entries); the killed among them are skipped
             for (size_t i = n_kill_old; i < old_ids.size(); i++) {
-                const uint8_t* rec = oldbuf.data() + i * stride;
-                if (!((const uint32_t*)rec)[0]) continue; // killed
-                std::string k;
-                encode_key(rec, k);
-                std::vector<uint8_t> v;
-                encode_deg_val(rec, v);
-                dd[k] = std::move(v);
+                HostRow row{oldbuf.data() + i * stride};
+                if (row.hdr().alive) dd.put(encode_key(row), encode_deg_val(row));
             }
-            auto& dsp = deg_spill[s];
-            auto dput32 = [&](uint32_t x) {
-                for (int b = 0; b < 4; b++)
-                    dsp.push_back((uint8_t)(x >> (8 * b)));
-            };
-            for (auto& [k, v] : dd) {
-                dsp.push_back(v.has_value() ? 1 : 0);
-                dput32((uint32_t)k.size());
-                dsp.insert(dsp.end(), k.begin(), k.end());
-                dput32(v ? (uint32_t)v->size() : 0);
-                if (v) dsp.insert(dsp.end(), v->begin(), v->end());
-            }
+            dd.write(deg_spill[s]);
         }
         HIP_TRY(hipMemset(js.killed_cursor, 0, 4));
         flush_mark[s] = cur;
         return RW_OK;
     }
     std::vector<uint8_t> deg_spill[2];
+
+    // §8f-5 recovery of side s from its concatenated drains, degrees from
+    // the degree table's (optional) stream
+    int restore(int s, const uint8_t* buf, uint64_t len,
+                const uint8_t* deg_buf, uint64_t deg_len) {
+        rwcodec::FrameMap merged;
+        if (!rwcodec::merge_frames(buf, len, merged))
+            FAIL(RW_E_INVAL, "malformed spill stream");
+        // the degree is the row's last datum; a PUT without one is ignored
+        std::map<std::string, uint32_t> degs;
+        if (deg_buf && deg_len) {
+            bool ok = rwcodec::for_each_frame(
+                deg_buf, deg_len,
+                [&](uint8_t put, const uint8_t* k, uint32_t klen,
+                    const uint8_t* v, uint32_t vlen) {
+                    std::string key((const char*)k, klen);
+                    if (put && vlen >= 9 && v[vlen - 9] == 1) {
+                        uint64_t d = 0;
+                        for (int b = 0; b < 8; b++)
+                            d |= (uint64_t)v[vlen - 8 + b] << (8 * b);
+                        degs[key] = (uint32_t)d;
+                    } else if (!put) {
+                        degs.erase(key);
+                    }
+                });
+            if (!ok) FAIL(RW_E_INVAL, "malformed degree spill stream");
+        }
+        uint32_t n = (uint32_t)merged.size();
+        if (!n) return RW_OK;
+        int ncols = m.n_cols[s];
+        std::vector<std::vector<int64_t>> cols(ncols,
+                                               std::vector<int64_t>(n));
+        std::vector<std::vector<uint8_t>> valid(ncols,
+                                                std::vector<uint8_t>(n));
+        std::vector<uint32_t> degrees(n, 0);
+        // varchar columns: decoded strings as bytes + offsets per column
+        const uint32_t vcm = m.vc_mask[s];
+        std::vector<std::vector<uint8_t>> sbytes(ncols);
+        std::vector<std::vector<uint32_t>> soffs(ncols);
+        for (int c = 0; c < ncols; c++)
+            if ((vcm >> c) & 1) soffs[c].assign(1, 0);
+        uint32_t i = 0;
+        for (auto& [kbytes, val] : merged) {
+            rwcodec::RowReader rd{val.data(), val.size()};
+            for (int c = 0; c < ncols; c++) {
+                if ((vcm >> c) & 1) {
+                    bool null = false;
+                    const uint8_t* sp = nullptr;
+                    uint32_t slen = 0;
+                    if (!rd.str(&null, &sp, &slen))
+                        FAIL(RW_E_INVAL, "restore: bad varchar datum");
+                    if (sbytes[c].size() + (uint64_t)slen > UINT32_MAX)
+                        FAIL(RW_E_INVAL, "restore: column %d strings exceed "
+                                         "4 GiB in one call", c);
+                    sbytes[c].insert(sbytes[c].end(), sp, sp + slen);
+                    soffs[c].push_back((uint32_t)sbytes[c].size());
+                    valid[c][i] = !null;
+                    continue;
+                }
+                rwcodec::DatumC d;
+                if (!rd.datum(types[s][c], &d))
+                    FAIL(RW_E_INVAL, "restore: bad row datum");
+                cols[c][i] = d.null ? 0 : d.i;
+                valid[c][i] = !d.null;
+            }
+            auto di = degs.find(kbytes);
+            if (di != degs.end()) degrees[i] = di->second;
+            i++;
+        }
+        seen_input = true;
+        int rc;
+        JoinBatchDev b;
+        if (vcm) {
+            // varchar side: the decoded rows go through the upload path,
+            // which appends the strings to the arena and stages reference
+            // words
+            std::vector<RwVarlenData> vds(ncols);
+            std::vector<RwColumn> rcols(ncols);
+            std::vector<uint8_t> rops(n, RW_OP_INSERT);
+            for (int c = 0; c < ncols; c++) {
+                rcols[c].type = types[s][c];
+                rcols[c].valid = valid[c].data();
+                if ((vcm >> c) & 1) {
+                    vds[c] = RwVarlenData{soffs[c].data(), sbytes[c].data()};
+                    rcols[c].data = &vds[c];
+                } else {
+                    rcols[c].data = cols[c].data();
+                }
+            }
+            RwChunk rch{};
+            rch.n_rows = n;
+            rch.n_cols = (uint32_t)ncols;
+            rch.ops = rops.data();
+            rch.vis = nullptr;
+            rch.cols = rcols.data();
+            rc = upload(s, &rch, &b);
+            if (rc != RW_OK) return rc;
+            // the staged host buffers die with this scope
+            HIP_TRY(hipStreamSynchronize(stream));
+        } else {
+            rc = ensure_stage(s, n);
+            if (rc != RW_OK) return rc;
+            b = stage[s];
+            for (int c = 0; c < ncols; c++) {
+                HIP_TRY(hipMemcpy(b.col_vals[c], cols[c].data(),
+                                  (size_t)n * 8, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(b.col_valid[c], valid[c].data(), n,
+                                  hipMemcpyHostToDevice));
+            }
+        }
+        b.vis = nullptr;
+        b.n_rows = n;
+        DevOwner tmp;
+        uint32_t* ddeg = nullptr;
+        HIP_TRY(tmp.upload(&ddeg, degrees));
+        uint32_t blocks = (n + 255) / 256;
+        if (blocks > 2048) blocks = 2048;
+        join_restore_kernel<<<blocks, 256, 0, stream>>>(
+            b, side[s], m, s, ddeg, out.counters + 1);
+        int rcs = hipStreamSynchronize(stream) == hipSuccess ? RW_OK
+                                                             : RW_E_INTERNAL;
+        tmp.release(&ddeg);
+        if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "restore sync failed");
+        uint32_t ctr[2];
+        HIP_TRY(hipMemcpy(ctr, out.counters, 8, hipMemcpyDeviceToHost));
+        if (ctr[1]) FAIL(RW_E_INTERNAL, "restore overflow (code %u)", ctr[1]);
+        // restored rows predate the epoch: the next drain must not re-PUT
+        // them
+        uint32_t cur = 0;
+        HIP_TRY(hipMemcpy(&cur, side[s].row_cursor, 4, hipMemcpyDeviceToHost));
+        flush_mark[s] = cur;
+        return RW_OK;
+    }
 
     int drain_output() {
         uint32_t ctr[2];
@@ -8647,20 +8636,14 @@ int rw_hash_agg_watermark(void* h, uint32_t group_key_pos, int64_t val) {
         tmp.release_all();
         if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "agg clean sync failed");
         if (rcv != RW_OK) return rcv;
-        auto put32 = [&](uint32_t x) {
-            for (int b = 0; b < 4; b++)
-                agg->spill.push_back((uint8_t)(x >> (8 * b)));
-        };
+        std::vector<uint8_t> k;
         for (uint32_t i = 0; i < n; i++) {
-            agg->spill.push_back(0); // DELETE
-            std::vector<uint8_t> k;
+            k.clear();
             for (int w = 0; w < agg->KW; w++)
                 agg->encode_key_datum(k, true, w, i,
                                       ((recs[i].nulls >> w) & 1) != 0,
                                       recs[i].key[w]);
-            put32((uint32_t)k.size());
-            agg->spill.insert(agg->spill.end(), k.begin(), k.end());
-            put32(0);
+            rwcodec::put_frame(agg->spill, 0, k); // DELETE
         }
         if (!meta[1]) break; // no overflow: every slot cleaned
         crec_cap *= 4;
@@ -9102,146 +9085,7 @@ int rw_hash_join_restore(void* h, int side, const uint8_t* buf,
                          uint64_t deg_len) {
     auto* j = (HashJoin*)h;
     if (side != 0 && side != 1) FAIL(RW_E_INVAL, "bad side");
-    std::map<std::string, std::vector<uint8_t>> merged;
-    bool ok = rwcodec::for_each_frame(
-        buf, len,
-        [&](uint8_t put, const uint8_t* k, uint32_t klen, const uint8_t* v,
-            uint32_t vlen) {
-            std::string key((const char*)k, klen);
-            if (put)
-                merged[key].assign(v, v + vlen);
-            else
-                merged.erase(key);
-        });
-    if (!ok) FAIL(RW_E_INVAL, "malformed spill stream");
-    std::map<std::string, uint32_t> degs;
-    if (deg_buf && deg_len) {
-        ok = rwcodec::for_each_frame(
-            deg_buf, deg_len,
-            [&](uint8_t put, const uint8_t* k, uint32_t klen,
-                const uint8_t* v, uint32_t vlen) {
-                std::string key((const char*)k, klen);
-                if (put && vlen >= 9 && v[vlen - 9] == 1) {
-                    uint64_t d = 0;
-                    for (int b = 0; b < 8; b++)
-                        d |= (uint64_t)v[vlen - 8 + b] << (8 * b);
-                    degs[key] = (uint32_t)d;
-                } else if (!put) {
-                    degs.erase(key);
-                }
-            });
-        if (!ok) FAIL(RW_E_INVAL, "malformed degree spill stream");
-    }
-    uint32_t n = (uint32_t)merged.size();
-    if (!n) return RW_OK;
-    int ncols = j->m.n_cols[side];
-    std::vector<std::vector<int64_t>> cols(ncols,
-                                           std::vector<int64_t>(n));
-    std::vector<std::vector<uint8_t>> valid(ncols,
-                                            std::vector<uint8_t>(n));
-    std::vector<uint32_t> degrees(n, 0);
-    // varchar columns: decoded strings as bytes + offsets per column
-    const uint32_t vcm = j->m.vc_mask[side];
-    std::vector<std::vector<uint8_t>> sbytes(ncols);
-    std::vector<std::vector<uint32_t>> soffs(ncols);
-    for (int c = 0; c < ncols; c++)
-        if ((vcm >> c) & 1) soffs[c].assign(1, 0);
-    uint32_t i = 0;
-    for (auto& [kbytes, val] : merged) {
-        size_t off = 0;
-        for (int c = 0; c < ncols; c++) {
-            if ((vcm >> c) & 1) {
-                bool null = false;
-                const uint8_t* sp = nullptr;
-                uint32_t slen = 0;
-                size_t got = rwcodec::value_decode_str(
-                    val.data() + off, val.size() - off, &null, &sp, &slen);
-                if (!got) FAIL(RW_E_INVAL, "restore: bad varchar datum");
-                off += got;
-                if (sbytes[c].size() + (uint64_t)slen > UINT32_MAX)
-                    FAIL(RW_E_INVAL, "restore: column %d strings exceed "
-                                     "4 GiB in one call", c);
-                sbytes[c].insert(sbytes[c].end(), sp, sp + slen);
-                soffs[c].push_back((uint32_t)sbytes[c].size());
-                valid[c][i] = !null;
-                continue;
-            }
-            rwcodec::DatumC d;
-            size_t got = rwcodec::value_decode_datum(
-                val.data() + off, val.size() - off, j->types[side][c], &d);
-            if (!got) FAIL(RW_E_INVAL, "restore: bad row datum");
-            off += got;
-            cols[c][i] = d.null ? 0 : d.i;
-            valid[c][i] = !d.null;
-        }
-        auto di = degs.find(kbytes);
-        if (di != degs.end()) degrees[i] = di->second;
-        i++;
-    }
-    j->seen_input = true;
-    int rc;
-    JoinBatchDev b;
-    if (vcm) {
-        // varchar side: the decoded rows go through the upload path, which
-        // appends the strings to the arena and stages reference words
-        std::vector<RwVarlenData> vds(ncols);
-        std::vector<RwColumn> rcols(ncols);
-        std::vector<uint8_t> rops(n, RW_OP_INSERT);
-        for (int c = 0; c < ncols; c++) {
-            rcols[c].type = j->types[side][c];
-            rcols[c].valid = valid[c].data();
-            if ((vcm >> c) & 1) {
-                vds[c] = RwVarlenData{soffs[c].data(), sbytes[c].data()};
-                rcols[c].data = &vds[c];
-            } else {
-                rcols[c].data = cols[c].data();
-            }
-        }
-        RwChunk rch{};
-        rch.n_rows = n;
-        rch.n_cols = (uint32_t)ncols;
-        rch.ops = rops.data();
-        rch.vis = nullptr;
-        rch.cols = rcols.data();
-        rc = j->upload(side, &rch, &b);
-        if (rc != RW_OK) return rc;
-        // the staged host buffers die with this scope
-        HIP_TRY(hipStreamSynchronize(j->stream));
-    } else {
-        rc = j->ensure_stage(side, n);
-        if (rc != RW_OK) return rc;
-        b = j->stage[side];
-        for (int c = 0; c < ncols; c++) {
-            HIP_TRY(hipMemcpy(b.col_vals[c], cols[c].data(), (size_t)n * 8,
-                              hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(b.col_valid[c], valid[c].data(), n,
-                              hipMemcpyHostToDevice));
-        }
-    }
-    b.vis = nullptr;
-    b.n_rows = n;
-    DevOwner tmp;
-    uint32_t* ddeg = nullptr;
-    HIP_TRY(tmp.alloc(&ddeg, (size_t)n * 4));
-    HIP_TRY(hipMemcpy(ddeg, degrees.data(), (size_t)n * 4,
-                      hipMemcpyHostToDevice));
-    uint32_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    join_restore_kernel<<<blocks, 256, 0, j->stream>>>(
-        b, j->side[side], j->m, side, ddeg, j->out.counters + 1);
-    int rcs = hipStreamSynchronize(j->stream) == hipSuccess ? RW_OK
-                                                            : RW_E_INTERNAL;
-    tmp.release(&ddeg);
-    if (rcs != RW_OK) FAIL(RW_E_INTERNAL, "restore sync failed");
-    uint32_t ctr[2];
-    HIP_TRY(hipMemcpy(ctr, j->out.counters, 8, hipMemcpyDeviceToHost));
-    if (ctr[1]) FAIL(RW_E_INTERNAL, "restore overflow (code %u)", ctr[1]);
-    // restored rows predate the epoch: the next drain must not re-PUT them
-    uint32_t cur = 0;
-    HIP_TRY(hipMemcpy(&cur, j->side[side].row_cursor, 4,
-                      hipMemcpyDeviceToHost));
-    j->flush_mark[side] = cur;
-    return RW_OK;
+    return j->restore(side, buf, len, deg_buf, deg_len);
 }
 
 // §8f-4 memory reclamation: rebuild one side's record store and buckets
@@ -10236,66 +10080,97 @@ struct GroupTopN {
         if (kcur)
             HIP_TRY(hipMemcpy(kills.data(), sd.killed, (size_t)kcur * 4,
                               hipMemcpyDeviceToHost));
-        auto encode_key = [&](const uint8_t* rec, std::string& k) {
-            const uint32_t vb = ((const uint32_t*)rec)[2];
-            const int64_t* vals = (const int64_t*)(rec + 16);
-            std::vector<uint8_t> kb;
+        auto encode_key = [&](HostRow row) {
+            std::vector<uint8_t> k;
             for (int i = 0; i < m.KW; i++) {
                 uint8_t col = m.gk_cols[i];
-                rwcodec::DatumC d = rwcodec::datum_of_word(
-                    types[col], !((vb >> col) & 1), vals[col]);
-                rwcodec::memcmp_encode_datum(kb, types[col], d, {});
+                rwcodec::memcmp_encode_datum(k, types[col],
+                                             row.datum(types[col], col), {});
             }
             for (int i = 0; i < m.n_ck; i++) {
                 uint8_t col = m.ck_cols[i];
-                rwcodec::DatumC d = rwcodec::datum_of_word(
-                    types[col], !((vb >> col) & 1), vals[col]);
                 rwcodec::OrderType ot;
                 ot.desc = m.ck_desc[i] != 0;
-                rwcodec::memcmp_encode_datum(kb, types[col], d, ot);
+                rwcodec::memcmp_encode_datum(k, types[col],
+                                             row.datum(types[col], col), ot);
             }
-            k.assign((const char*)kb.data(), kb.size());
+            return k;
         };
-        auto encode_val = [&](const uint8_t* rec, std::vector<uint8_t>& v) {
-            const uint32_t vb = ((const uint32_t*)rec)[2];
-            const int64_t* vals = (const int64_t*)(rec + 16);
-            for (int c = 0; c < m.n_cols; c++) {
-                rwcodec::DatumC d = rwcodec::datum_of_word(
-                    types[c], !((vb >> c) & 1), vals[c]);
-                rwcodec::value_encode_datum(v, types[c], d);
-            }
+        auto encode_val = [&](HostRow row) {
+            std::vector<uint8_t> v;
+            for (int c = 0; c < m.n_cols; c++)
+                rwcodec::value_encode_datum(v, types[c],
+                                            row.datum(types[c], c));
+            return v;
         };
-        std::map<std::string, std::optional<std::vector<uint8_t>>> delta;
+        rwcodec::KeyedDelta delta;
         std::vector<uint8_t> oldrec(stride);
         for (uint32_t i = 0; i < kcur; i++) {
             if (kills[i] >= flush_mark) continue;
             HIP_TRY(hipMemcpy(oldrec.data(),
                               sd.rows + (size_t)kills[i] * stride, stride,
                               hipMemcpyDeviceToHost));
-            std::string k;
-            encode_key(oldrec.data(), k);
-            delta[k] = std::nullopt;
+            delta.del(encode_key({oldrec.data()}));
         }
         for (uint32_t i = flush_mark; i < cur; i++) {
-            const uint8_t* rec = fresh.data() + (size_t)(i - flush_mark) * stride;
-            if (!((const uint32_t*)rec)[0]) continue;
-            std::string k;
-            encode_key(rec, k);
-            std::vector<uint8_t> v;
-            encode_val(rec, v);
-            delta[k] = std::move(v);
+            HostRow row{fresh.data() + (size_t)(i - flush_mark) * stride};
+            if (row.hdr().alive) delta.put(encode_key(row), encode_val(row));
         }
-        auto put32 = [&](uint32_t x) {
-            for (int b2 = 0; b2 < 4; b2++) sp.push_back((uint8_t)(x >> (8 * b2)));
-        };
-        for (auto& [k, v] : delta) {
-            sp.push_back(v.has_value() ? 1 : 0);
-            put32((uint32_t)k.size());
-            sp.insert(sp.end(), k.begin(), k.end());
-            put32(v ? (uint32_t)v->size() : 0);
-            if (v) sp.insert(sp.end(), v->begin(), v->end());
-        }
+        delta.write(sp);
         HIP_TRY(hipMemset(sd.killed_cursor, 0, 4));
+        flush_mark = cur;
+        return RW_OK;
+    }
+
+    // §8f-5 recovery: replay one or more concatenated epoch drains into a
+    // fresh executor. PUT/DELETE frames net host-side (last write wins, as a
+    // KV store compaction would); the surviving rows rebuild the device
+    // state and are marked persisted so the next drain does not re-PUT them.
+    int restore(const uint8_t* buf, uint64_t len) {
+        rwcodec::FrameMap merged;
+        if (!rwcodec::merge_frames(buf, len, merged))
+            FAIL(RW_E_INVAL, "malformed spill stream");
+        uint32_t n = (uint32_t)merged.size();
+        if (!n) return RW_OK;
+        int ncols = m.n_cols;
+        std::vector<std::vector<int64_t>> cols(ncols, std::vector<int64_t>(n));
+        std::vector<std::vector<uint8_t>> valid(ncols, std::vector<uint8_t>(n));
+        uint32_t i = 0;
+        for (auto& [kbytes, val] : merged) {
+            (void)kbytes;
+            rwcodec::RowReader rd{val.data(), val.size()};
+            for (int c = 0; c < ncols; c++) {
+                rwcodec::DatumC d;
+                if (!rd.datum(types[c], &d))
+                    FAIL(RW_E_INVAL, "restore: bad row datum");
+                cols[c][i] = d.null ? 0 : rwcodec::word_of_datum(types[c], d);
+                valid[c][i] = !d.null;
+            }
+            i++;
+        }
+        int rc = ensure_caps(n);
+        if (rc != RW_OK) return rc;
+        JoinBatchDev b = stage;
+        for (int c = 0; c < ncols; c++) {
+            HIP_TRY(hipMemcpy(b.col_vals[c], cols[c].data(), (size_t)n * 8,
+                              hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(b.col_valid[c], valid[c].data(), n,
+                              hipMemcpyHostToDevice));
+        }
+        b.vis = nullptr;
+        b.n_rows = n;
+        HIP_TRY(hipMemset(tcounters, 0, 8));
+        uint32_t blocks = (n + 255) / 256;
+        if (blocks > 2048) blocks = 2048;
+        topn_restore_kernel<<<blocks, 256, 0, stream>>>(b, sd, m,
+                                                        tcounters + 1);
+        if (hipStreamSynchronize(stream) != hipSuccess)
+            FAIL(RW_E_INTERNAL, "restore sync failed");
+        uint32_t tc[2];
+        HIP_TRY(hipMemcpy(tc, tcounters, 8, hipMemcpyDeviceToHost));
+        if (tc[1]) FAIL(RW_E_INTERNAL, "restore overflow (code %u)", tc[1]);
+        uint32_t cur = 0;
+        HIP_TRY(hipMemcpy(&cur, sd.row_cursor, 4, hipMemcpyDeviceToHost));
         flush_mark = cur;
         return RW_OK;
     }
@@ -10317,69 +10192,8 @@ int rw_topn_checkpoint_drain(void* h, uint8_t** buf, uint64_t* len) {
     return spill_export(sp, buf, len);
 }
 
-// §8f-5 recovery: replay one or more concatenated epoch drains into a fresh
-// GroupTopN executor. PUT/DELETE frames net host-side (last write wins, as a
-// KV store compaction would); the surviving rows rebuild the device state
-// and are marked persisted so the next drain does not re-PUT them.
 int rw_topn_restore(void* h, const uint8_t* buf, uint64_t len) {
-    auto* t = (GroupTopN*)h;
-    std::map<std::string, std::vector<uint8_t>> merged;
-    bool ok = rwcodec::for_each_frame(
-        buf, len,
-        [&](uint8_t put, const uint8_t* k, uint32_t klen, const uint8_t* v,
-            uint32_t vlen) {
-            std::string key((const char*)k, klen);
-            if (put)
-                merged[key].assign(v, v + vlen);
-            else
-                merged.erase(key);
-        });
-    if (!ok) FAIL(RW_E_INVAL, "malformed spill stream");
-    uint32_t n = (uint32_t)merged.size();
-    if (!n) return RW_OK;
-    int ncols = t->m.n_cols;
-    std::vector<std::vector<int64_t>> cols(ncols, std::vector<int64_t>(n));
-    std::vector<std::vector<uint8_t>> valid(ncols, std::vector<uint8_t>(n));
-    uint32_t i = 0;
-    for (auto& [kbytes, val] : merged) {
-        (void)kbytes;
-        size_t off = 0;
-        for (int c = 0; c < ncols; c++) {
-            rwcodec::DatumC d;
-            size_t got = rwcodec::value_decode_datum(
-                val.data() + off, val.size() - off, t->types[c], &d);
-            if (!got) FAIL(RW_E_INVAL, "restore: bad row datum");
-            off += got;
-            cols[c][i] = d.null ? 0 : rwcodec::word_of_datum(t->types[c], d);
-            valid[c][i] = !d.null;
-        }
-        i++;
-    }
-    int rc = t->ensure_caps(n);
-    if (rc != RW_OK) return rc;
-    JoinBatchDev b = t->stage;
-    for (int c = 0; c < ncols; c++) {
-        HIP_TRY(hipMemcpy(b.col_vals[c], cols[c].data(), (size_t)n * 8,
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b.col_valid[c], valid[c].data(), n,
-                          hipMemcpyHostToDevice));
-    }
-    b.vis = nullptr;
-    b.n_rows = n;
-    HIP_TRY(hipMemset(t->tcounters, 0, 8));
-    uint32_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    topn_restore_kernel<<<blocks, 256, 0, t->stream>>>(b, t->sd, t->m,
-                                                       t->tcounters + 1);
-    if (hipStreamSynchronize(t->stream) != hipSuccess)
-        FAIL(RW_E_INTERNAL, "restore sync failed");
-    uint32_t tc[2];
-    HIP_TRY(hipMemcpy(tc, t->tcounters, 8, hipMemcpyDeviceToHost));
-    if (tc[1]) FAIL(RW_E_INTERNAL, "restore overflow (code %u)", tc[1]);
-    uint32_t cur = 0;
-    HIP_TRY(hipMemcpy(&cur, t->sd.row_cursor, 4, hipMemcpyDeviceToHost));
-    t->flush_mark = cur;
-    return RW_OK;
+    return ((GroupTopN*)h)->restore(buf, len);
 }
 
 void* rw_group_top_n_create(const RwGroupTopNDesc* d) {

@@ -57,6 +57,19 @@ public:
         return e;
     }
 
+    // alloc sized to a host vector + blocking copy of it (an empty vector
+    // yields nullptr); on a failed copy the buffer stays recorded, so the
+    // owner still frees it
+    template <class T>
+    hipError_t upload(T** slot, const std::vector<T>& h) {
+        *slot = nullptr;
+        if (h.empty()) return hipSuccess;
+        size_t bytes = h.size() * sizeof(T);
+        hipError_t e = alloc(slot, bytes);
+        if (e != hipSuccess) return e;
+        return hipMemcpy(*slot, h.data(), bytes, hipMemcpyHostToDevice);
+    }
+
     // free now (hipFree synchronises the device), forget, null the slot
     template <class T>
     void release(T** slot) {
