@@ -400,4 +400,22 @@ inline void write_sorted(Bytes& out, std::vector<FrameRec>& rs) {
     for (auto& e : rs) put_frame(out, e.put, e.k, e.v);
 }
 
+// Re-emit a frame stream in bytewise key order, stable: a PUT and a DELETE of
+// one key within an epoch (EOWC mid-window PUT, then the window-close DELETE)
+// keep their order. A malformed stream is left as it is.
+inline void sort_spill_frames(Bytes& sp) {
+    std::vector<FrameRec> rs;
+    if (!for_each_frame(sp.data(), sp.size(),
+                        [&](uint8_t put, const uint8_t* k, uint32_t klen,
+                            const uint8_t* v, uint32_t vlen) {
+                            rs.push_back({put, Bytes(k, k + klen),
+                                          Bytes(v, v + vlen)});
+                        }))
+        return;
+    Bytes out;
+    out.reserve(sp.size());
+    write_sorted(out, rs);
+    sp.swap(out);
+}
+
 } // namespace rwcodec

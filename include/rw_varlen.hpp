@@ -11,6 +11,9 @@
 // pointers, so growing the arena is a reallocate + copy: no word changes.
 #pragma once
 #include <cstdint>
+#include <vector>
+
+#include "rw_chunk.h"
 
 #ifdef __HIPCC__
 #define RW_VARLEN_HD __host__ __device__
@@ -58,6 +61,30 @@ inline const char* validate_offsets(const uint32_t* offsets, uint32_t n_rows) {
             return "string longer than 2^24-1 bytes";
     }
     return nullptr;
+}
+
+// The input contract of one RW_T_VARCHAR column of n_rows rows: `data` set,
+// well-formed offsets, and a byte buffer wherever there are bytes. Returns
+// nullptr or the reason; the caller says which column. Every executor and
+// entry point that accepts varchar columns checks them with this.
+inline const char* check_column(const RwColumn& col, uint32_t n_rows) {
+    auto* vd = (const RwVarlenData*)col.data;
+    if (!vd) return "data is NULL";
+    if (const char* why = validate_offsets(vd->offsets, n_rows)) return why;
+    if (vd->offsets[n_rows] && !vd->bytes) return "bytes is NULL";
+    return nullptr;
+}
+
+// Reference words of one uploaded varchar column whose bytes were placed at
+// `base`: pack(flag | (base + offset), length) for a valid row, 0 for NULL.
+// `flag` is 0 or PROV_BIT.
+inline void ref_words(const RwVarlenData* vd, const uint8_t* valid, uint32_t n,
+                      uint64_t base, uint64_t flag, std::vector<int64_t>& out) {
+    out.resize(n);
+    for (uint32_t r = 0; r < n; r++)
+        out[r] = valid[r] ? (int64_t)pack(flag | (base + vd->offsets[r]),
+                                          vd->offsets[r + 1] - vd->offsets[r])
+                          : 0;
 }
 
 } // namespace rwvarlen

@@ -33,6 +33,7 @@
 
 #include <rocprim/device/device_scan.hpp>
 
+#include "../../include/rw_chunkbuild.hpp"
 #include "../../include/rw_codec.hpp"
 #include "../../include/rw_stream.h"
 #include "../../include/rw_varlen.hpp"
@@ -80,6 +81,32 @@ static int stage_regrow(DevOwner& mem, Batch& b, int n_cols, size_t cap,
     return RW_OK;
 }
 
+// One host column's n values of `width` bytes (8, or 16 for decimals) and its
+// valid bytes, to one slot of a staging batch.
+static int upload_col(int64_t* d_vals, uint8_t* d_valid, const void* vals,
+                      const uint8_t* valid, uint32_t n, size_t width,
+                      hipStream_t stream) {
+    HIP_TRY(hipMemcpyAsync(d_vals, vals, (size_t)n * width,
+                           hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_valid, valid, n, hipMemcpyHostToDevice, stream));
+    return RW_OK;
+}
+
+// The tail of every chunk upload: ops, then vis (a null b.vis tells the
+// kernels that every row is visible), then the row count. `b` is the caller's
+// copy of its staging batch.
+template <class Batch>
+static int upload_ops_vis(Batch& b, const RwChunk* c, hipStream_t stream) {
+    uint32_t n = c->n_rows;
+    HIP_TRY(hipMemcpyAsync(b.ops, c->ops, n, hipMemcpyHostToDevice, stream));
+    if (c->vis)
+        HIP_TRY(hipMemcpyAsync(b.vis, c->vis, n, hipMemcpyHostToDevice, stream));
+    else
+        b.vis = nullptr;
+    b.n_rows = n;
+    return RW_OK;
+}
+
 // A caller-owned device batch (the bench preload handles): the
 // kernel-argument struct, which is what the handle points at, and beside it
 // the owner of the batch's buffers.
@@ -91,6 +118,14 @@ struct Owned : Batch {
 static bool gpu_ok() {
     int n = 0;
     return hipGetDeviceCount(&n) == hipSuccess && n > 0;
+}
+
+// 256-thread blocks for `work` items: at least 1, at most 2048 (G11: cap +
+// grid-stride)
+static int grid_for(uint32_t work) {
+    uint32_t blocks = (work + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    return (int)(blocks ? blocks : 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -2617,7 +2652,7 @@ struct HashAgg {
     EventRing ring; // ring.ms_total: apply kernel time
     uint64_t apply_launches = 0, apply_rows = 0;
     // pending outputs
-    std::vector<RwChunk*> outq;
+    rwchunk::ChunkQueue outq;
     // checkpoint spill buffer (§8f-2): state-table KV deltas, accumulated at
     // flush, drained by rw_agg_checkpoint_drain
     std::vector<uint8_t> spill;
@@ -2644,12 +2679,6 @@ struct HashAgg {
     std::vector<uint8_t> distinct_col_types; // datum col type per table
     std::vector<uint32_t*> ddirty_flag, ddirty_list, ddirty_n;
     std::vector<std::vector<uint8_t>> dedup_persisted;
-
-    int grid_for(uint32_t work) const {
-        uint32_t blocks = (work + 255) / 256;
-        if (blocks > 2048) blocks = 2048; // G11: cap + grid-stride
-        return (int)(blocks ? blocks : 1);
-    }
 
     // ----- varchar group keys: interning state -----
     uint32_t vc_mask = 0; // bit i: group-key position i is varchar
@@ -2851,14 +2880,9 @@ struct HashAgg {
             uint32_t ci = group_key[vpos[j]];
             if (c->cols[ci].type != RW_T_VARCHAR)
                 FAIL(RW_E_INVAL, "column %u: expected a varchar column", ci);
-            auto* vd = (const RwVarlenData*)c->cols[ci].data;
-            const char* why = vd ? rwvarlen::validate_offsets(vd->offsets,
-                                                              c->n_rows)
-                                 : "data is NULL";
-            if (why) FAIL(RW_E_INVAL, "varchar column %u: %s", ci, why);
-            if (c->n_rows && vd->offsets[c->n_rows] && !vd->bytes)
-                FAIL(RW_E_INVAL, "varchar column %u: bytes is NULL", ci);
-            total += c->n_rows ? vd->offsets[c->n_rows] : 0;
+            if (const char* why = rwvarlen::check_column(c->cols[ci], c->n_rows))
+                FAIL(RW_E_INVAL, "varchar column %u: %s", ci, why);
+            total += ((const RwVarlenData*)c->cols[ci].data)->offsets[c->n_rows];
         }
         *total_bytes = total;
         return RW_OK;
@@ -3193,31 +3217,18 @@ struct HashAgg {
                 if (total)
                     HIP_TRY(hipMemcpyAsync(in_stg + vbase, vd->bytes, total,
                                            hipMemcpyHostToDevice, stream));
-                auto& w = vwords[bi];
-                w.resize(n);
-                for (uint32_t r = 0; r < n; r++)
-                    w[r] = col.valid[r]
-                               ? (int64_t)rwvarlen::pack(
-                                     rwvarlen::PROV_BIT |
-                                         (vbase + vd->offsets[r]),
-                                     vd->offsets[r + 1] - vd->offsets[r])
-                               : 0;
+                rwvarlen::ref_words(vd, col.valid, n, vbase, rwvarlen::PROV_BIT,
+                                    vwords[bi]);
                 vbase += total;
-                HIP_TRY(hipMemcpyAsync(b.col_vals[bi], w.data(), (size_t)n * 8,
-                                       hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(b.col_valid[bi], col.valid, n,
-                                       hipMemcpyHostToDevice, stream));
-                return RW_OK;
+                return upload_col(b.col_vals[bi], b.col_valid[bi],
+                                  vwords[bi].data(), col.valid, n, 8, stream);
             }
             size_t w = 8;
             if (col.type == RW_T_DECIMAL) w = 16; // 2 words/row
             else if (col.type != RW_T_I64 && col.type != RW_T_TS)
                 FAIL(RW_E_INVAL, "column type %d unsupported on GPU", col.type);
-            HIP_TRY(hipMemcpyAsync(b.col_vals[bi], col.data, (size_t)n * w,
-                                   hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(b.col_valid[bi], col.valid, n,
-                                   hipMemcpyHostToDevice, stream));
-            return RW_OK;
+            return upload_col(b.col_vals[bi], b.col_valid[bi], col.data,
+                              col.valid, n, w, stream);
         };
         for (int i = 0; i < KW; i++) {
             int rc = upcol(i, group_key[i]);
@@ -3237,13 +3248,8 @@ struct HashAgg {
                 if (rc != RW_OK) return rc;
             }
         }
-        HIP_TRY(hipMemcpyAsync(b.ops, c->ops, n, hipMemcpyHostToDevice, stream));
-        if (c->vis) {
-            HIP_TRY(hipMemcpyAsync(b.vis, c->vis, n, hipMemcpyHostToDevice, stream));
-        } else {
-            b.vis = nullptr;
-        }
-        b.n_rows = n;
+        int rc = upload_ops_vis(b, c, stream);
+        if (rc != RW_OK) return rc;
         // dense fast path: every row visible, Insert, and non-null in every
         // referenced column — the kernel then skips the three byte streams
         b.dense = (c->vis == nullptr);
@@ -3794,7 +3800,8 @@ struct HashAgg {
                     so[m] = RW_OP_INSERT;
                     m++;
                 }
-                slice_outputs(sv, sn, so, m);
+                int rcs = slice_outputs(sv, sn, so, m);
+                if (rcs != RW_OK) return rcs;
             }
             HIP_TRY(hipMemset(t.counters, 0, 12));
             return RW_OK;
@@ -3827,7 +3834,8 @@ struct HashAgg {
                                   vals2.size() * 8, hipMemcpyDeviceToHost));
             }
             spill_records(vals, nulls, ops, n_out, vals2);
-            slice_outputs(vals, nulls, ops, n_out, vals2);
+            int rcs = slice_outputs(vals, nulls, ops, n_out, vals2);
+            if (rcs != RW_OK) return rcs;
         }
         HIP_TRY(hipMemset(t.counters, 0, 12));
         return RW_OK;
@@ -4648,101 +4656,44 @@ struct HashAgg {
         return RW_OK;
     }
 
-    // Host-side chunking with the U-pair no-split rule
-    // (stream_chunk_builder.rs:188-218)
-    void slice_outputs(const std::vector<long long>& vals,
-                       const std::vector<uint8_t>& nulls,
-                       const std::vector<uint8_t>& ops, uint32_t n_out,
-                       const std::vector<long long>& vals2 = {}) {
-        uint32_t start = 0;
+    // Cuts the row-major output block into chunks of chunk_size rows (0 =
+    // 1024) under the U-pair rule and queues them.
+    int slice_outputs(const std::vector<long long>& vals,
+                      const std::vector<uint8_t>& nulls,
+                      const std::vector<uint8_t>& ops, uint32_t n_out,
+                      const std::vector<long long>& vals2 = {}) {
         uint32_t max_rows = desc.chunk_size ? desc.chunk_size : 1024;
-        while (start < n_out) {
-            uint32_t take = n_out - start;
-            if (take > max_rows) {
-                take = max_rows;
-                // don't split a U−/U+ pair: if the last row taken is U−,
-                // extend by one (the builder's size max+1 case)
-                if (ops[start + take - 1] == RW_OP_UPDATE_DELETE) take += 1;
+        for (auto [start, n] : rwchunk::slice_ranges(n_out, max_rows, ops.data())) {
+            rwchunk::Builder cb(n, (uint32_t)out_width);
+            for (int ci = 0; ci < out_width; ci++) {
+                size_t ix = (size_t)start * out_width + ci;
+                auto valid = rwchunk::from_nulls(&nulls[ix], out_width);
+                auto* v = (const int64_t*)&vals[ix];
+                if (out_types[ci] == RW_T_DECIMAL && !vals2.empty())
+                    cb.decimal(v, (const int64_t*)&vals2[ix], out_width, valid);
+                else if (ci < KW && ((vc_mask >> ci) & 1)) {
+                    // a varchar key column: the strings fetch_key_strings
+                    // left in vk_offs / vk_bytes, in block row order
+                    if (!cb.varchar(&vk_offs[ci][start], vk_bytes[ci].data(),
+                                    nullptr, valid))
+                        FAIL(RW_E_INTERNAL, "output chunk strings exceed 4 GiB; "
+                                            "lower chunk_size");
+                } else
+                    cb.fixed(out_types[ci], v, out_width, valid);
             }
-            outq.push_back(make_chunk(vals, nulls, ops, start, take, vals2));
-            start += take;
+            cb.ops(&ops[start]);
+            outq.push(cb.release());
         }
+        return RW_OK;
     }
 
-    RwChunk* make_chunk(const std::vector<long long>& vals,
-                        const std::vector<uint8_t>& nulls,
-                        const std::vector<uint8_t>& ops, uint32_t start,
-                        uint32_t n,
-                        const std::vector<long long>& vals2 = {}) {
-        auto* ch = new RwChunk();
-        auto* cols = new RwColumn[out_width];
-        auto* o = new uint8_t[n];
-        memcpy(o, ops.data() + start, n);
-        for (int ci = 0; ci < out_width; ci++) {
-            uint8_t ty = out_types[ci];
-            if (ty == RW_T_DECIMAL && !vals2.empty()) {
-                auto* data = new int64_t[(size_t)2 * n];
-                auto* valid = new uint8_t[n];
-                for (uint32_t r = 0; r < n; r++) {
-                    size_t ix = (size_t)(start + r) * out_width + ci;
-                    valid[r] = !nulls[ix];
-                    data[2 * r] = vals[ix];
-                    data[2 * r + 1] = vals2[ix];
-                }
-                cols[ci].type = ty;
-                cols[ci].valid = valid;
-                cols[ci].data = data;
-                continue;
-            }
-            if (ci < KW && ((vc_mask >> ci) & 1)) {
-                // a varchar key column: offsets rebased to this chunk's
-                // first row; NULL rows have zero length
-                const auto& so = vk_offs[ci];
-                uint64_t base = so[start], total = so[start + n] - base;
-                auto* offs = new uint32_t[(size_t)n + 1];
-                auto* bytes = new uint8_t[total ? total : 1];
-                auto* valid = new uint8_t[n];
-                for (uint32_t r = 0; r <= n; r++)
-                    offs[r] = (uint32_t)(so[start + r] - base);
-                if (total) memcpy(bytes, vk_bytes[ci].data() + base, total);
-                for (uint32_t r = 0; r < n; r++)
-                    valid[r] = !nulls[(size_t)(start + r) * out_width + ci];
-                cols[ci].type = ty;
-                cols[ci].valid = valid;
-                cols[ci].data = new RwVarlenData{offs, bytes};
-                continue;
-            }
-            auto* data = new int64_t[n];
-            auto* valid = new uint8_t[n];
-            for (uint32_t r = 0; r < n; r++) {
-                data[r] = vals[(size_t)(start + r) * out_width + ci];
-                valid[r] = !nulls[(size_t)(start + r) * out_width + ci];
-            }
-            cols[ci].type = out_types[ci];
-            cols[ci].valid = valid;
-            cols[ci].data = data;
-        }
-        ch->n_rows = n;
-        ch->n_cols = out_width;
-        ch->ops = o;
-        ch->vis = nullptr;
-        ch->cols = cols;
-        return ch;
-    }
-
-    RwChunk* poll() {
-        if (outq.empty()) return nullptr;
-        RwChunk* c = outq.front();
-        outq.erase(outq.begin());
-        return c;
-    }
+    RwChunk* poll() { return outq.poll(); }
 
     ~HashAgg() {
         for (auto ev : in_ev)
             if (ev) hipEventDestroy(ev);
         mem.release_all(); // device memory goes before the stream
         if (stream) hipStreamDestroy(stream);
-        for (auto* c : outq) rw_chunk_free(c);
     }
 };
 
@@ -4763,67 +4714,11 @@ static int spill_export(const std::vector<uint8_t>& sp, uint8_t** buf,
     return RW_OK;
 }
 
-// Re-emit a spill stream ([put u8][klen u32 LE][key][vlen u32 LE][val] frames)
-// in memcomparable-key order. stable: a PUT and DELETE of the same key within
-// one epoch (EOWC mid-window PUT then window-close DELETE) keep their order.
-static void sort_spill_frames(std::vector<uint8_t>& sp) {
-    struct Frame { const uint8_t* p; size_t n; };
-    std::vector<Frame> frames;
-    size_t off = 0;
-    auto rd32 = [&](size_t o) {
-        return (uint32_t)sp[o] | ((uint32_t)sp[o + 1] << 8) |
-               ((uint32_t)sp[o + 2] << 16) | ((uint32_t)sp[o + 3] << 24);
-    };
-    while (off + 5 <= sp.size()) {
-        size_t start = off;
-        uint32_t klen = rd32(off + 1);
-        off += 5 + klen;
-        if (off + 4 > sp.size()) return; // malformed: leave unsorted
-        uint32_t vlen = rd32(off);
-        off += 4 + vlen;
-        if (off > sp.size()) return;
-        frames.push_back({sp.data() + start, off - start});
-    }
-    std::stable_sort(frames.begin(), frames.end(), [](const Frame& a,
-                                                      const Frame& b) {
-        uint32_t ka = (uint32_t)a.p[1] | ((uint32_t)a.p[2] << 8) |
-                      ((uint32_t)a.p[3] << 16) | ((uint32_t)a.p[4] << 24);
-        uint32_t kb = (uint32_t)b.p[1] | ((uint32_t)b.p[2] << 8) |
-                      ((uint32_t)b.p[3] << 16) | ((uint32_t)b.p[4] << 24);
-        int c = memcmp(a.p + 5, b.p + 5, ka < kb ? ka : kb);
-        if (c) return c < 0;
-        return ka < kb;
-    });
-    std::vector<uint8_t> out;
-    out.reserve(sp.size());
-    for (auto& f : frames) out.insert(out.end(), f.p, f.p + f.n);
-    sp.swap(out);
-}
-
 extern "C" {
 
 const char* rw_last_error(void) { return g_err.c_str(); }
 
-void rw_chunk_free(RwChunk* ch) {
-    if (!ch) return;
-    for (uint32_t c = 0; c < ch->n_cols; c++) {
-        delete[] ch->cols[c].valid;
-        if (ch->cols[c].type == RW_T_VARCHAR) {
-            auto* vd = (const RwVarlenData*)ch->cols[c].data;
-            if (vd) {
-                delete[] vd->offsets;
-                delete[] vd->bytes;
-                delete vd;
-            }
-        } else {
-            delete[] (int64_t*)ch->cols[c].data;
-        }
-    }
-    delete[] ch->cols;
-    delete[] ch->ops;
-    delete[] ch->vis;
-    delete ch;
-}
+void rw_chunk_free(RwChunk* ch) { rwchunk::free_chunk(ch); }
 
 void* rw_hash_agg_create(const RwHashAggDesc* d) {
     auto* h = new HashAgg();
@@ -5212,7 +5107,7 @@ int rw_agg_checkpoint_drain(void* h, uint8_t** buf, uint64_t* len) {
     // guarantee): the flush kernel's atomic-cursor emission order is
     // nondeterministic, so the canonical sorted form is what both this and
     // the oracle emit — enabling byte-compare parity.
-    sort_spill_frames(agg->spill);
+    rwcodec::sort_spill_frames(agg->spill);
     int rc = spill_export(agg->spill, buf, len);
     if (rc != RW_OK) return rc;
     agg->spill.clear();
@@ -5440,15 +5335,9 @@ static int vnode_compute_varlen(const RwVnodeDesc* d, const RwChunk* chunk,
         if (c.type == RW_T_BOOL || c.type == RW_T_DECIMAL)
             FAIL(RW_E_INVAL, "vnode key type %d unsupported on GPU", c.type);
         if (c.type != RW_T_VARCHAR) continue;
-        auto* vd = (const RwVarlenData*)c.data;
-        if (!vd) FAIL(RW_E_INVAL, "varchar vnode key (column %u): no data",
-                      d->key_indices[k]);
-        if (const char* why = rwvarlen::validate_offsets(vd->offsets, n))
+        if (const char* why = rwvarlen::check_column(c, n))
             FAIL(RW_E_INVAL, "varchar vnode key (column %u): %s",
                  d->key_indices[k], why);
-        if (vd->offsets[n] && !vd->bytes)
-            FAIL(RW_E_INVAL, "varchar vnode key (column %u): bytes is NULL",
-                 d->key_indices[k]);
     }
     if (d->vnode_count < 1 || d->vnode_count > 65536)
         FAIL(RW_E_INVAL, "vnode_count %u (1..65536)", d->vnode_count);
@@ -5495,10 +5384,8 @@ static int vnode_compute_varlen(const RwVnodeDesc* d, const RwChunk* chunk,
     b.n_rows = n;
     uint16_t* dout;
     HIP_TRY(da.alloc(&dout, (size_t)n * 2));
-    uint32_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    vnode_varlen_kernel<<<blocks, 256>>>(b, (int)d->n_keys, d->vnode_count,
-                                         dout);
+    vnode_varlen_kernel<<<grid_for(n), 256>>>(b, (int)d->n_keys,
+                                              d->vnode_count, dout);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 2, hipMemcpyDeviceToHost));
@@ -5540,11 +5427,8 @@ int rw_vnode_compute(const RwVnodeDesc* d, const RwChunk* chunk, uint16_t* out) 
     b.n_rows = n;
     uint16_t* dout;
     HIP_TRY(da.alloc(&dout, (size_t)n * 2));
-    uint32_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (!blocks) blocks = 1;
-    vnode_kernel<<<blocks, 256>>>(b, (int)d->n_keys, d->vnode_count, dout,
-                                  types[0], types[1], types[2], types[3]);
+    vnode_kernel<<<grid_for(n), 256>>>(b, (int)d->n_keys, d->vnode_count, dout,
+                                       types[0], types[1], types[2], types[3]);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 2, hipMemcpyDeviceToHost));
     return RW_OK;
@@ -5568,12 +5452,8 @@ int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
     uint32_t n = chunk->n_rows;
     for (uint32_t c = 0; c < chunk->n_cols; c++) {
         if (chunk->cols[c].type != RW_T_VARCHAR) continue;
-        auto* vd = (const RwVarlenData*)chunk->cols[c].data;
-        if (!vd) FAIL(RW_E_INVAL, "dispatch: varchar column %u has no data", c);
-        if (const char* why = rwvarlen::validate_offsets(vd->offsets, n))
+        if (const char* why = rwvarlen::check_column(chunk->cols[c], n))
             FAIL(RW_E_INVAL, "dispatch: varchar column %u: %s", c, why);
-        if (vd->offsets[n] && !vd->bytes)
-            FAIL(RW_E_INVAL, "dispatch: varchar column %u: bytes is NULL", c);
     }
     std::vector<uint16_t> vnodes(n);
     int rc = rw_vnode_compute(&d->v, chunk, vnodes.data());
@@ -5618,7 +5498,7 @@ int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
     uint32_t built = 0;
     try {
         // a varchar column's output form, built once: NULL rows zero length
-        std::vector<std::vector<uint32_t>> voffs(chunk->n_cols);
+        std::vector<std::vector<uint64_t>> voffs(chunk->n_cols);
         std::vector<std::vector<uint8_t>> vbytes(chunk->n_cols);
         for (uint32_t c = 0; c < chunk->n_cols; c++) {
             if (chunk->cols[c].type != RW_T_VARCHAR) continue;
@@ -5630,51 +5510,28 @@ int rw_dispatch_compute(const RwDispatchDesc* d, const RwChunk* chunk,
                     vbytes[c].insert(vbytes[c].end(),
                                      vd->bytes + vd->offsets[r],
                                      vd->bytes + vd->offsets[r + 1]);
-                voffs[c][r + 1] = (uint32_t)vbytes[c].size();
+                voffs[c][r + 1] = vbytes[c].size();
             }
         }
+        std::vector<uint8_t> vis(n);
         for (uint32_t o = 0; o < d->n_outputs; o++) {
-            // the chunk is freeable by rw_chunk_free at every point below
-            auto* ch = new RwChunk();
-            outs[o] = ch;
-            built = o + 1;
-            auto* cols = new RwColumn[chunk->n_cols]();
-            ch->cols = cols;
-            ch->n_rows = n;
+            rwchunk::Builder cb(n, chunk->n_cols);
             for (uint32_t c = 0; c < chunk->n_cols; c++) {
-                cols[c].type = chunk->cols[c].type;
-                ch->n_cols = c + 1;
-                auto* valid = new uint8_t[n];
-                cols[c].valid = valid;
-                memcpy(valid, chunk->cols[c].valid, n);
-                if (cols[c].type == RW_T_VARCHAR) {
-                    auto* vd = new RwVarlenData();
-                    vd->offsets = nullptr;
-                    vd->bytes = nullptr;
-                    cols[c].data = vd;
-                    auto* offs = new uint32_t[(size_t)n + 1];
-                    vd->offsets = offs;
-                    memcpy(offs, voffs[c].data(), ((size_t)n + 1) * 4);
-                    auto* bytes = new uint8_t[vbytes[c].size() + 1];
-                    vd->bytes = bytes;
-                    if (!vbytes[c].empty())
-                        memcpy(bytes, vbytes[c].data(), vbytes[c].size());
-                } else {
-                    uint32_t sz = rw_type_size(cols[c].type);
-                    // freed as int64_t* by rw_chunk_free
-                    auto* data = new int64_t[((size_t)n * sz + 7) / 8];
-                    cols[c].data = data;
-                    memcpy(data, chunk->cols[c].data, (size_t)n * sz);
-                }
+                const RwColumn& col = chunk->cols[c];
+                auto valid = rwchunk::from_valid(col.valid);
+                if (col.type == RW_T_VARCHAR)
+                    // never refused: voffs[c][n] <= the input's 32-bit total
+                    (void)cb.varchar(voffs[c].data(), vbytes[c].data(), nullptr,
+                                     valid);
+                else
+                    cb.raw(col.type, col.data, valid);
             }
-            ch->n_cols = chunk->n_cols;
-            auto* op_arr = new uint8_t[n];
-            ch->ops = op_arr;
-            memcpy(op_arr, ops.data(), n);
-            auto* vis = new uint8_t[n];
-            ch->vis = vis;
+            cb.ops(ops.data());
             for (uint32_t r = 0; r < n; r++)
                 vis[r] = visible(r) && d->vnode_to_output[vnodes[r]] == o ? 1 : 0;
+            cb.vis(vis.data());
+            outs[o] = cb.release();
+            built = o + 1;
         }
     } catch (const std::bad_alloc&) {
         for (uint32_t o = 0; o < built; o++) {
@@ -7390,7 +7247,7 @@ struct HashJoin {
     // staging
     JoinBatchDev stage[2]{};
     uint32_t stage_cap[2] = {0, 0};
-    std::vector<RwChunk*> outq;
+    rwchunk::ChunkQueue outq;
     uint8_t* zeros = nullptr; // all-zero null flags for pipeline dummy cols
     uint8_t* d_vnode_bitmap = nullptr; // rescale scope (update_vnode_bitmap)
     uint16_t* d_vnode_hop = nullptr;   // q7-pipeline exchange-hop vnodes
@@ -7656,18 +7513,15 @@ struct HashJoin {
             if (!((m.vc_mask[s] >> ci) & 1)) continue;
             if (c->cols[ci].type != RW_T_VARCHAR)
                 FAIL(RW_E_INVAL, "column %d: expected a varchar column", ci);
-            auto* vd = (const RwVarlenData*)c->cols[ci].data;
-            const char* why =
-                vd ? rwvarlen::validate_offsets(vd->offsets, n) : "data is NULL";
-            if (why) FAIL(RW_E_INVAL, "varchar column %d: %s", ci, why);
-            if (n && vd->offsets[n] && !vd->bytes)
-                FAIL(RW_E_INVAL, "varchar column %d: bytes is NULL", ci);
+            if (const char* why = rwvarlen::check_column(c->cols[ci], n))
+                FAIL(RW_E_INVAL, "varchar column %d: %s", ci, why);
         }
         seen_input = true;
         int rc = ensure_stage(s, n);
         if (rc != RW_OK) return rc;
         JoinBatchDev b = stage[s];
         for (int ci = 0; ci < m.n_cols[s]; ci++) {
+            const void* vals = c->cols[ci].data;
             if ((m.vc_mask[s] >> ci) & 1) {
                 // append the chunk's bytes at the arena tail (one H2D copy)
                 // and stage reference words where i64 values go
@@ -7681,31 +7535,16 @@ struct HashJoin {
                                            total, hipMemcpyHostToDevice,
                                            stream));
                 arena_used[s] += total;
-                auto& w = vwords[s][ci];
-                w.resize(n);
-                for (uint32_t r = 0; r < n; r++)
-                    w[r] = c->cols[ci].valid[r]
-                               ? (int64_t)rwvarlen::pack(
-                                     base + vd->offsets[r],
-                                     vd->offsets[r + 1] - vd->offsets[r])
-                               : 0;
-                HIP_TRY(hipMemcpyAsync(b.col_vals[ci], w.data(), (size_t)n * 8,
-                                       hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(b.col_valid[ci], c->cols[ci].valid, n,
-                                       hipMemcpyHostToDevice, stream));
-                continue;
+                rwvarlen::ref_words(vd, c->cols[ci].valid, n, base, 0,
+                                    vwords[s][ci]);
+                vals = vwords[s][ci].data();
             }
-            HIP_TRY(hipMemcpyAsync(b.col_vals[ci], c->cols[ci].data, (size_t)n * 8,
-                                   hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(b.col_valid[ci], c->cols[ci].valid, n,
-                                   hipMemcpyHostToDevice, stream));
+            rc = upload_col(b.col_vals[ci], b.col_valid[ci], vals,
+                            c->cols[ci].valid, n, 8, stream);
+            if (rc != RW_OK) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(b.ops, c->ops, n, hipMemcpyHostToDevice, stream));
-        if (c->vis)
-            HIP_TRY(hipMemcpyAsync(b.vis, c->vis, n, hipMemcpyHostToDevice, stream));
-        else
-            b.vis = nullptr;
-        b.n_rows = n;
+        rc = upload_ops_vis(b, c, stream);
+        if (rc != RW_OK) return rc;
         b.all_insert = 1;
         for (uint32_t r = 0; r < n && b.all_insert; r++)
             if (!(c->vis && !c->vis[r]) && c->ops[r] != RW_OP_INSERT &&
@@ -7896,9 +7735,8 @@ struct HashJoin {
             DevOwner tmp;
             HIP_TRY(tmp.upload(&d_ids, old_ids));
             HIP_TRY(tmp.alloc(&d_out, oldbuf.size()));
-            uint32_t gblocks = ((uint32_t)old_ids.size() + 255) / 256;
-            if (gblocks > 2048) gblocks = 2048;
-            jgather_rows_kernel<<<gblocks, 256, 0, stream>>>(
+            jgather_rows_kernel<<<grid_for((uint32_t)old_ids.size()), 256, 0,
+                                  stream>>>(
                 js, d_ids, (uint32_t)old_ids.size(), d_out);
             int rcg = hipMemcpy(oldbuf.data(), d_out, oldbuf.size(),
                                 hipMemcpyDeviceToHost);
@@ -8069,9 +7907,7 @@ struct HashJoin {
         DevOwner tmp;
         uint32_t* ddeg = nullptr;
         HIP_TRY(tmp.upload(&ddeg, degrees));
-        uint32_t blocks = (n + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        join_restore_kernel<<<blocks, 256, 0, stream>>>(
+        join_restore_kernel<<<grid_for(n), 256, 0, stream>>>(
             b, side[s], m, s, ddeg, out.counters + 1);
         int rcs = hipStreamSynchronize(stream) == hipSuccess ? RW_OK
                                                              : RW_E_INTERNAL;
@@ -8159,66 +7995,34 @@ struct HashJoin {
                 HIP_TRY(hipMemset(out.counters, 0, 8));
                 return RW_OK;
             }
+            // chunk_size rows each (0 = 1024, at least 2); join output has
+            // no U-pair rule
             uint32_t max_rows = desc.chunk_size ? desc.chunk_size : 1024;
             if (max_rows < 2) max_rows = 2;
-            for (uint32_t start = 0; start < n_out; start += max_rows) {
-                uint32_t take = n_out - start;
-                if (take > max_rows) take = max_rows;
-                auto* ch = new RwChunk();
-                auto* cols = new RwColumn[m.n_out];
-                auto* o = new uint8_t[take];
-                memcpy(o, ops.data() + start, take);
+            for (auto [start, take] :
+                 rwchunk::slice_ranges(n_out, max_rows, nullptr)) {
+                rwchunk::Builder cb(take, (uint32_t)m.n_out);
                 for (int ci = 0; ci < m.n_out; ci++) {
-                    if (out_types[ci] == RW_T_VARCHAR) {
-                        // slice the packed buffer: this chunk's own bytes
-                        // with offsets rebased to 0
-                        const auto& vo = voffs[ci];
-                        auto blk = [&](uint32_t r) {
-                            return src_idx.empty() ? start + r
-                                                   : src_idx[start + r];
-                        };
-                        uint64_t tot = 0;
-                        for (uint32_t r = 0; r < take; r++)
-                            tot += vo[blk(r) + 1] - vo[blk(r)];
-                        if (tot > UINT32_MAX)
-                            FAIL(RW_E_INTERNAL,
-                                 "output chunk strings exceed 4 GiB; lower "
-                                 "chunk_size");
-                        auto* offs = new uint32_t[take + 1];
-                        auto* bytes = new uint8_t[tot ? tot : 1];
-                        auto* valid = new uint8_t[take];
-                        uint32_t at = 0;
-                        for (uint32_t r = 0; r < take; r++) {
-                            uint64_t o0 = vo[blk(r)], o1 = vo[blk(r) + 1];
-                            offs[r] = at;
-                            if (o1 > o0)
-                                memcpy(bytes + at, vbytes[ci].data() + o0,
-                                       o1 - o0);
-                            at += (uint32_t)(o1 - o0);
-                            valid[r] = !nulls[(size_t)ci * n_out + start + r];
-                        }
-                        offs[take] = at;
-                        cols[ci].type = RW_T_VARCHAR;
-                        cols[ci].valid = valid;
-                        cols[ci].data = new RwVarlenData{offs, bytes};
+                    size_t ix = (size_t)ci * n_out + start;
+                    auto valid = rwchunk::from_nulls(&nulls[ix], 1);
+                    if (out_types[ci] != RW_T_VARCHAR) {
+                        cb.fixed(out_types[ci], &vals[ix], 1, valid);
                         continue;
                     }
-                    auto* data = new int64_t[take];
-                    auto* valid = new uint8_t[take];
-                    for (uint32_t r = 0; r < take; r++) {
-                        data[r] = vals[(size_t)ci * n_out + start + r];
-                        valid[r] = !nulls[(size_t)ci * n_out + start + r];
-                    }
-                    cols[ci].type = out_types[ci];
-                    cols[ci].valid = valid;
-                    cols[ci].data = data;
+                    // the strings of this chunk's rows, found in the
+                    // uncompacted block through src_idx
+                    bool ok = src_idx.empty()
+                                  ? cb.varchar(&voffs[ci][start],
+                                               vbytes[ci].data(), nullptr, valid)
+                                  : cb.varchar(voffs[ci].data(),
+                                               vbytes[ci].data(),
+                                               &src_idx[start], valid);
+                    if (!ok)
+                        FAIL(RW_E_INTERNAL, "output chunk strings exceed 4 GiB; "
+                                            "lower chunk_size");
                 }
-                ch->n_rows = take;
-                ch->n_cols = m.n_out;
-                ch->ops = o;
-                ch->vis = nullptr;
-                ch->cols = cols;
-                outq.push_back(ch);
+                cb.ops(&ops[start]);
+                outq.push(cb.release());
             }
         }
         HIP_TRY(hipMemset(out.counters, 0, 8));
@@ -8389,10 +8193,8 @@ struct HashJoin {
         }
         auto run_segment = [&](uint32_t r0, uint32_t r1) -> int {
             if (!del_before.empty() && del_before[r1] != del_before[r0]) {
-                uint32_t blocks = (r1 - r0 + 255) / 256;
-                if (blocks > 2048) blocks = 2048;
-                join_varlen_resolve_kernel<<<blocks, 256, 0, stream>>>(
-                    b, side[s], m, s, r0, r1);
+                join_varlen_resolve_kernel<<<grid_for(r1 - r0), 256, 0,
+                                             stream>>>(b, side[s], m, s, r0, r1);
             }
             return probe(s, b, true, r0, r1);
         };
@@ -8495,17 +8297,11 @@ struct HashJoin {
         return RW_OK;
     }
 
-    RwChunk* poll() {
-        if (outq.empty()) return nullptr;
-        RwChunk* c = outq.front();
-        outq.erase(outq.begin());
-        return c;
-    }
+    RwChunk* poll() { return outq.poll(); }
 
     ~HashJoin() {
         mem.release_all(); // device memory goes before the stream
         if (stream) hipStreamDestroy(stream);
-        for (auto* c : outq) rw_chunk_free(c);
     }
 };
 
@@ -8883,9 +8679,7 @@ int rw_join_apply_aggout(void* join_h, void* agg_h, int side,
     b.all_insert = 0; // change stream carries U-/U+ pairs
     b.unique_keys = 0;
     b.no_insert = 0;
-    uint32_t blocks = ((uint32_t)n_rows + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    aggout_to_join_kernel<<<blocks, 256, 0, j->stream>>>(
+    aggout_to_join_kernel<<<grid_for((uint32_t)n_rows), 256, 0, j->stream>>>(
         agg->t.out_vals, agg->t.out_nulls, agg->t.out_ops, (uint32_t)n_rows,
         agg->out_width, cm, b);
     return j->probe(side, b, true, 0, (uint32_t)n_rows);
@@ -9747,7 +9541,7 @@ struct GroupTopN {
     std::vector<uint32_t> ck_col_idx;
     uint32_t chunk_size;
     hipStream_t stream = nullptr;
-    std::vector<RwChunk*> outq;
+    rwchunk::ChunkQueue outq;
 
     int init(const RwGroupTopNDesc* d) {
         if (!gpu_ok())
@@ -9831,7 +9625,6 @@ struct GroupTopN {
     ~GroupTopN() {
         mem.release_all(); // device memory goes before the stream
         if (stream) hipStreamDestroy(stream);
-        for (auto* c : outq) rw_chunk_free(c);
     }
 
     int ensure_caps(uint32_t n) {
@@ -9897,36 +9690,24 @@ struct GroupTopN {
         if (ensure_caps(n) != RW_OK) return RW_E_INTERNAL;
         JoinBatchDev b = stage;
         for (int i = 0; i < m.n_cols; i++) {
-            HIP_TRY(hipMemcpyAsync(b.col_vals[i], c->cols[i].data,
-                                   (size_t)n * 8, hipMemcpyHostToDevice,
-                                   stream));
-            HIP_TRY(hipMemcpyAsync(b.col_valid[i], c->cols[i].valid, n,
-                                   hipMemcpyHostToDevice, stream));
+            int rc = upload_col(b.col_vals[i], b.col_valid[i], c->cols[i].data,
+                                c->cols[i].valid, n, 8, stream);
+            if (rc != RW_OK) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(b.ops, c->ops, n, hipMemcpyHostToDevice,
-                               stream));
-        if (c->vis)
-            HIP_TRY(hipMemcpyAsync(b.vis, c->vis, n, hipMemcpyHostToDevice,
-                                   stream));
-        else
-            b.vis = nullptr;
-        b.n_rows = n;
+        int rc = upload_ops_vis(b, c, stream);
+        if (rc != RW_OK) return rc;
         HIP_TRY(hipMemsetAsync(tcounters, 0, 8, stream));
 
-        uint32_t blocks = (n + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        topn_touch_kernel<<<blocks, 256, 0, stream>>>(b, sd, m, touched,
-                                                      touched_list, tcounters);
+        topn_touch_kernel<<<grid_for(n), 256, 0, stream>>>(
+            b, sd, m, touched, touched_list, tcounters);
         topn_snapshot_kernel<<<256, 256, 0, stream>>>(
             sd, m, touched_list, tcounters, old_win, old_n, tcounters + 1);
         auto segs = conflict_segments(c);
         uint32_t start = 0;
         auto launch_apply = [&](uint32_t a, uint32_t z) {
             if (z <= a) return;
-            uint32_t bl = (z - a + 255) / 256;
-            if (bl > 2048) bl = 2048;
-            topn_apply_kernel<<<bl, 256, 0, stream>>>(b, sd, m, a, z,
-                                                      tcounters);
+            topn_apply_kernel<<<grid_for(z - a), 256, 0, stream>>>(b, sd, m, a, z,
+                                                                   tcounters);
         };
         for (uint32_t bnd : segs) {
             launch_apply(start, bnd);
@@ -9962,37 +9743,18 @@ struct GroupTopN {
                               hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(ops.data(), out.ops, n_out,
                               hipMemcpyDeviceToHost));
+            // chunk_size rows each (at least 2), U-/U+ pairs kept together
             uint32_t max_rows = chunk_size < 2 ? 2 : chunk_size;
-            uint32_t s = 0;
-            while (s < n_out) {
-                uint32_t take = n_out - s;
-                if (take > max_rows) take = max_rows;
-                // U-pair adjacency: never split a U-/U+ pair at the edge
-                if (s + take < n_out &&
-                    ops[s + take - 1] == RW_OP_UPDATE_DELETE)
-                    take++;
-                auto* ch = new RwChunk();
-                auto* cols = new RwColumn[m.n_cols];
-                auto* o = new uint8_t[take];
-                memcpy(o, ops.data() + s, take);
+            for (auto [s, take] :
+                 rwchunk::slice_ranges(n_out, max_rows, ops.data())) {
+                rwchunk::Builder cb(take, (uint32_t)m.n_cols);
                 for (int ci = 0; ci < m.n_cols; ci++) {
-                    auto* data = new int64_t[take];
-                    auto* valid = new uint8_t[take];
-                    for (uint32_t r = 0; r < take; r++) {
-                        data[r] = vals[(size_t)(s + r) * m.n_cols + ci];
-                        valid[r] = !nulls[(size_t)(s + r) * m.n_cols + ci];
-                    }
-                    cols[ci].type = types[ci];
-                    cols[ci].valid = valid;
-                    cols[ci].data = data;
+                    size_t ix = (size_t)s * m.n_cols + ci;
+                    cb.fixed(types[ci], &vals[ix], m.n_cols,
+                             rwchunk::from_nulls(&nulls[ix], m.n_cols));
                 }
-                ch->n_rows = take;
-                ch->n_cols = (uint32_t)m.n_cols;
-                ch->ops = o;
-                ch->vis = nullptr;
-                ch->cols = cols;
-                outq.push_back(ch);
-                s += take;
+                cb.ops(&ops[s]);
+                outq.push(cb.release());
             }
         }
         HIP_TRY(hipMemset(out.counters, 0, 8));
@@ -10040,11 +9802,8 @@ struct GroupTopN {
         HIP_TRY(hipMemcpy(sd.row_cursor, &n_alive, 4,
                           hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(tcounters, 0, 8, stream));
-        uint32_t blocks = (n_alive + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        if (!blocks) blocks = 1;
-        topn_relink_kernel<<<blocks, 256, 0, stream>>>(sd, m, n_alive,
-                                                       tcounters + 1);
+        topn_relink_kernel<<<grid_for(n_alive), 256, 0, stream>>>(
+            sd, m, n_alive, tcounters + 1);
         if (hipStreamSynchronize(stream) != hipSuccess)
             FAIL(RW_E_INTERNAL, "topn compact relink failed");
         uint32_t tc[2];
@@ -10160,10 +9919,8 @@ struct GroupTopN {
         b.vis = nullptr;
         b.n_rows = n;
         HIP_TRY(hipMemset(tcounters, 0, 8));
-        uint32_t blocks = (n + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        topn_restore_kernel<<<blocks, 256, 0, stream>>>(b, sd, m,
-                                                        tcounters + 1);
+        topn_restore_kernel<<<grid_for(n), 256, 0, stream>>>(b, sd, m,
+                                                             tcounters + 1);
         if (hipStreamSynchronize(stream) != hipSuccess)
             FAIL(RW_E_INTERNAL, "restore sync failed");
         uint32_t tc[2];
@@ -10175,12 +9932,7 @@ struct GroupTopN {
         return RW_OK;
     }
 
-    RwChunk* poll() {
-        if (outq.empty()) return nullptr;
-        RwChunk* c = outq.front();
-        outq.erase(outq.begin());
-        return c;
-    }
+    RwChunk* poll() { return outq.poll(); }
 };
 
 extern "C" {

@@ -248,6 +248,58 @@ static void check_writers() {
                                {0, {0x80}, {}}}));
 }
 
+// sort_spill_frames: stable, bytewise key order (a prefix before its
+// extensions), a malformed stream left as it was
+static void check_sort_frames() {
+    Bytes s = write_frames({{1, {0x80}, B("p80")},
+                            {1, B("k"), B("mid-window put")},
+                            {1, {0x7f, 0x00}, B("ext")},
+                            {0, B("k"), {}},
+                            {1, {0x7f}, B("prefix")},
+                            {0, {0x80}, {}},
+                            {1, {}, B("empty key")}});
+    Bytes sorted = write_frames({{1, {}, B("empty key")},
+                                 {1, B("k"), B("mid-window put")},
+                                 {0, B("k"), {}},
+                                 {1, {0x7f}, B("prefix")},
+                                 {1, {0x7f, 0x00}, B("ext")},
+                                 {1, {0x80}, B("p80")},
+                                 {0, {0x80}, {}}});
+    Bytes got = s;
+    got.shrink_to_fit();
+    rwcodec::sort_spill_frames(got);
+    CHECK(got == sorted);
+    rwcodec::sort_spill_frames(got); // sorted already: unchanged
+    CHECK(got == sorted);
+    // the other order under one key stays the other order
+    Bytes dp = write_frames({{0, B("k"), {}}, {1, B("k"), B("v")}, {1, {}, {}}});
+    rwcodec::sort_spill_frames(dp);
+    CHECK(dp == write_frames({{1, {}, {}}, {0, B("k"), {}}, {1, B("k"), B("v")}}));
+    // a malformed tail, at every cut of the last frame and with stray bytes
+    // after it: the buffer is left as it was
+    for (size_t cut = 1; cut < 5 + 1 + 4 + 3; cut++) {
+        Bytes bad(s.begin(), s.end() - cut);
+        Bytes before = bad;
+        rwcodec::sort_spill_frames(bad);
+        CHECK(bad == before);
+    }
+    for (size_t extra = 1; extra <= 4; extra++) {
+        Bytes bad = s;
+        bad.insert(bad.end(), extra, 0x01);
+        Bytes before = bad;
+        rwcodec::sort_spill_frames(bad);
+        CHECK(bad == before);
+    }
+    Bytes huge = s; // a key length that runs past the end
+    huge[1] = huge[2] = huge[3] = huge[4] = 0xff;
+    Bytes before = huge;
+    rwcodec::sort_spill_frames(huge);
+    CHECK(huge == before);
+    Bytes none;
+    rwcodec::sort_spill_frames(none);
+    CHECK(none.empty());
+}
+
 static void check_row_reader() {
     const long long dec_lo = 0x0123456789abcdefLL, dec_hi = -7;
     const double f = -1234.5e-3;
@@ -332,6 +384,7 @@ int main() {
     check_truncation();
     check_merge();
     check_writers();
+    check_sort_frames();
     check_row_reader();
     if (g_fail) {
         fprintf(stderr, "%d check(s) failed\n", g_fail);

@@ -1655,3 +1655,126 @@ def test_topn_float_group_key_zero_identity_gpu():
     # zero group limit 2: of v=1,2,6 only the two smallest stay
     ops = [r[0] for r in results["gpu"][0]]
     assert ops.count("+") >= 4  # zero group 2 + nan group 2 + 1.5 group 1
+
+
+# ---------------- output slicing at chunk_size = 2 ----------------
+#
+# Every drained output block is cut into chunks of at most chunk_size rows; an
+# executor under the U-pair rule (HashAgg, GroupTopN) lets a chunk that would
+# end on a U- with rows still to come take the U+ too. The join has no pair
+# rule. The oracle's chunk boundaries are its own: only the row multiset is
+# compared across the two. Whether a U- lands on a chunk edge here depends on
+# the device's emission order, so these cases may pass without one extended
+# chunk; the rule itself is pinned row by row in chunk_build_host_check.cpp.
+
+
+def _slicer_chunk_count(ops, max_rows, pair_rule):
+    n, s, k = len(ops), 0, 0
+    while s < n:
+        take = min(max_rows, n - s)
+        if pair_rule and s + take < n and ops[s + take - 1] == ffi.OP_UPDATE_DELETE:
+            take += 1
+        s += take
+        k += 1
+    return k
+
+
+def _check_slicing(chunks, chunk_size, pair_rule):
+    """chunks: what one drain (a push, or a flush) left to poll."""
+    for c in chunks:
+        ops = [int(x) for x in c.ops]
+        tail_pair = ops[-2:] == [ffi.OP_UPDATE_DELETE, ffi.OP_UPDATE_INSERT]
+        assert len(ops) <= chunk_size or (len(ops) == chunk_size + 1 and tail_pair), ops
+        if pair_rule:
+            assert ops[-1] != ffi.OP_UPDATE_DELETE, ops
+        else:
+            assert len(ops) <= chunk_size, ops
+    all_ops = [int(x) for c in chunks for x in c.ops]
+    assert len(chunks) == _slicer_chunk_count(all_ops, chunk_size, pair_rule), (
+        [len(c.ops) for c in chunks], all_ops)
+    return all_ops
+
+
+def _i64_chunk(ops, *cols):
+    return mk_chunk([T_I64] * len(cols), np.asarray(ops, np.uint8),
+                    [np.asarray(c, np.int64) for c in cols])
+
+
+def test_topn_slicing_chunk_size_2():
+    # group, order column, key column, and a payload outside the cache key: a
+    # top whose payload is rewritten leaves as a U-/U+ pair, a top that a
+    # smaller row displaces as an Insert and a Delete
+    types = [T_I64, T_I64, T_I64, T_I64]
+    mk = lambda lib: ffi.GroupTopN(lib, types, [0], [(1, False)], [(2, False)],
+                                   limit=1, chunk_size=2)
+    g, o = mk(gpu()), mk(oracle())
+    I, D = ffi.OP_INSERT, ffi.OP_DELETE
+    pushes = [
+        # four groups, two rows each; the second row of a group beats the first
+        _i64_chunk([I] * 8, [1, 1, 2, 2, 3, 3, 4, 4],
+                   [20, 10, 21, 11, 22, 12, 23, 13], list(range(8)), [7] * 8),
+        # a new group, group 1's top rewritten, group 2's top displaced
+        _i64_chunk([I, D, I, I], [0, 1, 1, 2], [50, 10, 10, 5], [8, 1, 1, 9],
+                   [7, 7, 70, 7]),
+    ]
+    seen = []
+    for i, c in enumerate(pushes):
+        g.push(c)
+        o.push(c)
+        got = g.poll_all()
+        assert rows_multiset(got) == rows_multiset(o.poll_all()), f"push {i}"
+        seen.append(_check_slicing(got, 2, pair_rule=True))
+    g.close()
+    o.close()
+    assert len(seen[0]) == 4 and set(seen[0]) == {ffi.OP_INSERT}
+    assert sorted(seen[1]) == [I, I, D, ffi.OP_UPDATE_DELETE, ffi.OP_UPDATE_INSERT]
+
+
+def test_agg_slicing_chunk_size_2():
+    calls = [(AGG_COUNT_STAR, -1, T_I64), (AGG_SUM, 1, T_I64)]
+    mk = lambda lib: ffi.HashAgg(lib, [T_I64, T_I64], [0], calls, 0,
+                                 chunk_size=2, append_only=False)
+    g, o = mk(gpu()), mk(oracle())
+    I, D = ffi.OP_INSERT, ffi.OP_DELETE
+    epochs = [
+        _i64_chunk([I] * 7, [1, 2, 3, 4, 5, 1, 2], [10, 20, 30, 40, 50, 11, 21]),
+        # groups 1, 2, 3 change (U-/U+); group 5 goes (its only row retracts)
+        _i64_chunk([I, D, I, D], [1, 2, 3, 5], [12, 21, 31, 50]),
+        # groups 1..4 change, group 5 comes back
+        _i64_chunk([D, I, D, I, I, I], [1, 2, 3, 4, 5, 5],
+                   [10, 22, 30, 41, 51, 52]),
+    ]
+    seen = []
+    for e, c in enumerate(epochs):
+        g.push(c)
+        o.push(c)
+        g.flush(e + 1)
+        o.flush(e + 1)
+        got = g.poll_all()
+        assert rows_multiset(got) == rows_multiset(o.poll_all()), f"epoch {e + 1}"
+        seen.append(_check_slicing(got, 2, pair_rule=True))
+    g.close()
+    o.close()
+    assert len(seen[0]) == 5 and set(seen[0]) == {I}
+    assert seen[1].count(ffi.OP_UPDATE_DELETE) == 3 and seen[1].count(D) == 1
+    assert seen[2].count(ffi.OP_UPDATE_DELETE) == 4 and seen[2].count(I) == 1
+
+
+def test_join_slicing_chunk_size_2():
+    g, o = join_pair(chunk_size=2)
+    pushes = [
+        (SIDE_LEFT, _i64_chunk([0] * 6, [1, 1, 2, 2, 3, 4], [0, 1, 2, 3, 4, 5])),
+        # keys 1 and 2 match two rows each, key 3 one, the rest none
+        (SIDE_RIGHT, _i64_chunk([0] * 6, [1, 7, 2, 8, 3, 9],
+                                [10, 11, 12, 13, 14, 15])),
+    ]
+    seen = []
+    for i, (side, c) in enumerate(pushes):
+        g.push(side, c)
+        o.push(side, c)
+        got = g.poll_all()
+        assert rows_multiset(got) == rows_multiset(o.poll_all()), f"push {i}"
+        seen.append(_check_slicing(got, 2, pair_rule=False))
+    g.close()
+    o.close()
+    assert seen[0] == [] and len(seen[1]) == 5
